@@ -3,13 +3,22 @@
 (heatmap encoders -> MVFEx/JQA refiners -> 2D-to-3D lifting), config `ego4view_syn_pose3d`,
 batch 64 per GPU, synthetic 256x256x4-view input resident in HBM, random-init weights (seeded).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-graph] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-graph] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU); inference shards the
 batch-of-frames axis with no data-path collective ("weak" scaling: B frames per GPU).  One JSON line
 is printed by rank 0.  A "step" is one forward of B frames.
 
-Extra objects on the line:
+A plain run sets up, warms up (W untimed steps), times exactly K steps and prints the line: metric / value / unit /
+higher_is_better / dtype / ms_per_step (milliseconds per timed step) with config and ranks.  --dump-outputs DIR then also writes
+what rank 0's last timed step returned (the seeded inputs are the same in every run with the same arguments, so two builds can be
+compared output for output): DIR/pred_pose3d_<i>.npy, every 3-D pose set of the forward in full, and DIR/pred_heatmap_<i>.npy,
+the initial / refined heat maps (B, 4, 15, 64, 64), in full up to 2^21 values each, above that a fixed seeded sample of 2^21
+values (flat indices drawn by torch.randint from torch.Generator().manual_seed(0), in draw order); float32 throughout.
+
+--full adds every other leg (each measured outside the timed steps, never part of `value`), as the extra objects below.
+
+Extra objects on the line (--full):
   roofline     — dominant kernel (the implicit-GEMM conv/linear entry point; "[f16x2]" = its fp16-scheme launches, which are
                  the bulk; the chained-1x1 launches of round 5 are booked with it): FLOPs of its launches / their summed
                  duration, measured with HIP events on the launch stream in an instrumented pass right after the timed region.
@@ -168,10 +177,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step (weak scaling: fixed as N grows)")
     ap.add_argument("--global-batch", type=int, default=0, help="strong scaling: frames per step over ALL GPUs (split evenly over the ranks); "
                                                                "0 = weak scaling with --batch frames per GPU")
-    ap.add_argument("--steady-steps", type=int, default=400, help="steps of the steady-state leg behind the timed burst (0 = skip)")
+    ap.add_argument("--steady-steps", type=int, default=400, help="steps of the steady-state leg behind the timed burst (--full; 0 = skip)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("EGR_BENCH_LANES", "2")),
                     help="captured forwards in flight (runner.PipelinedForward): consecutive steps overlap on that many streams")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run every leg outside the headline: live PMC passes, steady state, one lane, "
+                                                        "roofline, CPU baseline + parity census, preprocess, exact arithmetic, configs 1-3, "
+                                                        "training step (the --no-* options below select among them)")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) the profiled workload of the live PMC passes: --steps eager forwards, nothing else")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not measure roofline.traffic in this run (two rocprofv3 child passes, ~40 s); "
                                                                "replay the committed PMC summary instead")
@@ -549,6 +562,31 @@ def _gpu_time_ms(fn, warmup: int, iters: int, join=None) -> float:
     return e0.elapsed_time(e1) / iters
 
 
+DUMP_SAMPLE = 1 << 21      # values per dumped array at most (8 MB in float32): two heat-map sets stay far below 64 MB at any batch
+
+
+def dump_outputs(out, path: str) -> dict:
+    """--dump-outputs: the forward's (list of 3-D pose sets, list of heat-map sets) as DIR/pred_pose3d_<i>.npy and
+    DIR/pred_heatmap_<i>.npy in float32; an array of more than DUMP_SAMPLE values is replaced by the values at DUMP_SAMPLE flat
+    indices drawn from a fixed seed (the same indices in every run of the same shape).  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    preds, heatmaps = out
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for kind, arrays in (("pred_pose3d", preds), ("pred_heatmap", heatmaps)):
+        for i, t in enumerate(arrays):
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+                a = flat[idx.to(flat.device)].float().cpu().numpy()
+            else:
+                a = t.detach().float().cpu().numpy()
+            np.save(os.path.join(path, f"{kind}_{i}.npy"), a)
+            written[f"{kind}_{i}"] = list(a.shape)
+    return written
+
+
 def config_legs(args, dev, with_cpu: bool):
     """BASELINE.json configs 2 and 3 on this GPU (batch 32, hipGraph replay like the headline, HIP events) and the CPU leg of
     config 1.  Never part of `value`.  Each GPU leg carries its own parity object: the CPU oracle on a small sample of the same
@@ -841,7 +879,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     live_traffic, live_prov = None, None
-    if rank == 0 and world == 1 and not args.no_live_pmc and not args.no_graph and os.environ.get("EGR_BENCH_LIVE_PMC", "1") != "0":
+    if args.full and rank == 0 and world == 1 and not args.no_live_pmc and not args.no_graph and os.environ.get("EGR_BENCH_LIVE_PMC", "1") != "0":
         # (before anything here touches the GPU; --no-graph runs are the profiled ones themselves: no nesting)
         live_traffic, live_prov = live_pmc_traffic(args.batch if args.global_batch <= 0 else args.global_batch)
         if live_traffic is None:
@@ -867,7 +905,7 @@ def main():
     B = frames_per_rank(args.batch, args.global_batch, world)
     net = EgoPoseFormerMVFEX(**copy.deepcopy(configs.pose3d_cfg("ego4view_syn"))).eval()
     synth.load_synth(net, 42)
-    cpu_sd = {k: v.clone() for k, v in net.state_dict().items()} if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    cpu_sd = {k: v.clone() for k, v in net.state_dict().items()} if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     net = net.to(dev)
     img = synth.synth_images(B, 4, seed=1234 + rank).to(dev)  # each rank: its own shard of frames, resident in HBM
 
@@ -893,9 +931,10 @@ def main():
                 _log(f"lanes: {type(exc).__name__}: {exc} - falling back to one lane")
                 pipe, args.lanes = None, 1
                 torch.cuda.synchronize()
+        last = [None]      # what the latest step returned (--dump-outputs)
         if pipe is not None:
             def run():
-                pipe(img)
+                last[0] = pipe(img)
         elif use_graph:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -906,24 +945,27 @@ def main():
             _log("capturing hipGraph")
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                outs = step()
+                last[0] = step()       # static outputs of the graph: every replay rewrites them
             _log("captured")
             run = graph.replay
         else:
-            run = step
+            def run():
+                last[0] = step()
 
         from egorear_amd.dist import timed_steps
         own = {}
         elapsed = timed_steps(run, args.steps, args.warmup, torch.cuda.synchronize, dev if backend == "nccl" else None, detail=own)
+        if args.dump_outputs and rank == 0:      # (timed_steps ended in a device synchronise: the lanes' outputs are complete)
+            _log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(last[0], args.dump_outputs)}")
         # steady state: the same step over a few hundred iterations (clocks and temperature settled); never `value`
         steady = None
-        if args.steady_steps > 0:
+        if args.full and args.steady_steps > 0:
             el2 = timed_steps(run, args.steady_steps, 0, torch.cuda.synchronize, dev if backend == "nccl" else None)
             steady = {"steps": args.steady_steps, "value": round(world * B * args.steady_steps / el2, 2), "unit": "frames/s",
                       "ms_per_step": round(1e3 * el2 / args.steady_steps, 3)}
         # one lane: the same forward as ONE captured graph replayed back to back (what the second lane's overlap is worth; never `value`)
         one_lane = None
-        if rank == 0 and world == 1 and pipe is not None and args.steady_steps > 0:
+        if args.full and rank == 0 and world == 1 and pipe is not None and args.steady_steps > 0:
             try:
                 g1 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g1):
@@ -946,7 +988,7 @@ def main():
         roof = None
         kernels = {}
         _log(f"timed region done: {elapsed:.3f} s")
-        if rank == 0:
+        if args.full and rank == 0:
             hip.PROFILE = []
             step()
             torch.cuda.synchronize()
@@ -1010,7 +1052,7 @@ def main():
         except Exception as exc:
             cpu_line = {"error": f"{type(exc).__name__}: {exc}"}
     pre_leg = None
-    if rank == 0:
+    if args.full and rank == 0:
         # §8(f) rank 1, timed separately (never part of `value`): raw uint8 872x872 frames -> model input, on the GPU
         from egorear_amd.preprocess import FramePreprocessor
         pre = FramePreprocessor(device=dev)
@@ -1055,28 +1097,28 @@ def main():
         except Exception as exc:  # never at the expense of the main line
             pre_leg["from_raw_frames"] = {"error": f"{type(exc).__name__}: {exc}"}
     exact = None
-    if rank == 0 and world == 1 and W_FORMAT == "f16x2" and use_graph and not args.no_exact:
+    if args.full and rank == 0 and world == 1 and W_FORMAT == "f16x2" and use_graph and not args.no_exact:
         _log("exact-arithmetic leg (bf16x3)")
         try:
             exact = exact_leg(net, img, B, args.lanes)
         except Exception as exc:  # never at the expense of the main line
             exact = {"error": f"{type(exc).__name__}: {exc}"}
     cfg_legs = None
-    if rank == 0 and world == 1 and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         _log("config 2 / 3 legs (+ config 1 on the CPU)")
         try:
             cfg_legs = config_legs(args, dev, with_cpu=not args.no_cpu_baseline)
         except Exception as exc:  # never at the expense of the main line
             cfg_legs = {"error": f"{type(exc).__name__}: {exc}"}
     train = None
-    if not args.no_train and world > 1 and rccl_ok is False:
+    if args.full and not args.no_train and world > 1 and rccl_ok is False:
         # the step's gradient exchange is designed for RCCL over xGMI; a host-staged gloo all-reduce would be a different measurement
         train = {"skipped": "RCCL did not come up on this node (ranks.rccl_ok = false): the training leg's gradient all-reduce is not measured through gloo"}
-    elif not args.no_train:
+    elif args.full and not args.no_train:
         _log("training-step leg")
         try:
             import gc
-            del graph, run, step, net, img, pipe     # hand the inference state (graph pool, weights, inputs) back before the step allocates
+            del graph, run, step, net, img, pipe, last     # hand the inference state (graph pool, weights, inputs) back before the step allocates
             gc.collect()
             torch.cuda.empty_cache()
             train = train_leg(args, dev, rank, world, backend)
@@ -1096,51 +1138,47 @@ def main():
                        "launch": ("eager" if not use_graph else "hipGraph replay" if args.lanes <= 1 else
                                   f"{args.lanes} hipGraphs (one captured forward per lane) replayed round-robin on {args.lanes} streams: consecutive steps overlap"),
                        "arithmetic": ARITHMETIC},
-            "steady_state": steady,
-            "exact_leg": exact,
             "path_tflops_per_gpu": round(fps / world * GFLOP_PER_FRAME / 1e3, 2),
             "path_frac_of_f32_mfma_peak": round(fps / world * GFLOP_PER_FRAME / 1e3 / PEAK_F32_MFMA_TFLOPS, 4),  # > 1 is possible: most contractions run on the bf16 matrix cores
-            "roofline": roof,
-            "roofline_hbm": roofline_hbm(kernels, pre_leg),
             "ranks": ranks_obj,
-            "configs": cfg_legs,
-            "preprocess": pre_leg,
-            "train": train,
             # abs-max records refused because an arena ran out (each one a launch that silently left the fp16 scheme): 0 when healthy
             "amax_arena_exhausted": int(hip.ARENA_EXHAUSTED),
         }
-        if kernels:
-            line["kernel_ms"] = {n: round(v["ms"], 3) for n, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
-        line["one_lane"] = one_lane
-        line["cpu_baseline"], line["parity_vs_cpu_oracle"] = cpu_line, parity_line
-        # ---- everything a scalar-only parser must see, as SCALAR keys: at the top level (last, so that the tail of the line shows them)
-        # and - because the driver's record keeps `roofline` / `cpu_baseline` / `config` only - once more at the front of `roofline`
-        def _get(d, *path):
-            for k in path:
-                d = d.get(k) if isinstance(d, dict) else None
-            return d
-        tr_roof = _get(train, "roofline") or {}
-        scal = {      # (ordered by what a record that keeps only the first ~two dozen scalars of `roofline` must see)
-            "traffic_live": _get(roof, "traffic_live"), "mfma_busy_frac": _get(roof, "mfma_busy_frac"),
-            "mfma_busy_frac_conv3x3": _get(roof, "mfma_busy_frac_conv3x3"),
-            "frac_conv3x3": _get(roof, "frac_conv3x3"), "conv3x3_ms": _get(roof, "conv3x3_ms"),
-            "frac_conv1x1_hbm": _get(roof, "frac_conv1x1_hbm"), "conv1x1_ms": _get(roof, "conv1x1_ms"),
-            "exact_fps": _get(exact, "value"), "steady_fps": _get(steady, "value"), "one_lane_fps": _get(one_lane, "value"),
-            "train_ms_per_step": _get(train, "ms_per_step"), "train_frac": tr_roof.get("frac"),
-            "parity_frames": _get(parity_line, "frames"), "argmax_mismatches": _get(parity_line, "argmax_mismatches"),
-            "argmax_mismatches_outside_rounding": _get(parity_line, "argmax_mismatches_outside_rounding"),
-            "max_joint_err_cm": _get(parity_line, "max_joint_err_cm"),
-            "cfg2_fps": _get(cfg_legs, "config2_heatmap_4view", "value"), "cfg3_fps": _get(cfg_legs, "config3_heatmap_mvfex", "value"),
-            "train_fps": _get(train, "value"), "train_dominant_kernel": tr_roof.get("kernel"), "train_launches_per_step": _get(train, "launches_per_step"),
-            "argmax_compared": _get(parity_line, "argmax_compared"), "valid_mask_mismatches": _get(parity_line, "valid_mask_mismatches"),
-            "argmax_mismatches_fp64_sides_with_hip": _get(parity_line, "argmax_mismatches_fp64_sides_with_hip"),
-            "top2_gap_below_1e-5": _get(parity_line, "top2_gap_below_1e-5"),
-            "all_kernels_ms_per_step": _get(roof, "all_kernels_ms_per_step"), "launches_per_forward": len(prof) if rank == 0 else None,
-        }
-        if roof is not None:
-            head = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")
-            line["roofline"] = {**{k: roof[k] for k in head if k in roof}, **scal, **{k: v for k, v in roof.items() if k not in head and k not in scal}}
-        line.update(scal)
+        if args.full:
+            line.update({"steady_state": steady, "exact_leg": exact, "roofline": roof, "roofline_hbm": roofline_hbm(kernels, pre_leg),
+                         "configs": cfg_legs, "preprocess": pre_leg, "train": train})
+            if kernels:
+                line["kernel_ms"] = {n: round(v["ms"], 3) for n, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
+            line["one_lane"] = one_lane
+            line["cpu_baseline"], line["parity_vs_cpu_oracle"] = cpu_line, parity_line
+            # ---- everything a scalar-only parser must see, as SCALAR keys: at the top level (last, so that the tail of the line shows them)
+            # and - because the driver's record keeps `roofline` / `cpu_baseline` / `config` only - once more at the front of `roofline`
+            def _get(d, *path):
+                for k in path:
+                    d = d.get(k) if isinstance(d, dict) else None
+                return d
+            tr_roof = _get(train, "roofline") or {}
+            scal = {      # (ordered by what a record that keeps only the first ~two dozen scalars of `roofline` must see)
+                "traffic_live": _get(roof, "traffic_live"), "mfma_busy_frac": _get(roof, "mfma_busy_frac"),
+                "mfma_busy_frac_conv3x3": _get(roof, "mfma_busy_frac_conv3x3"),
+                "frac_conv3x3": _get(roof, "frac_conv3x3"), "conv3x3_ms": _get(roof, "conv3x3_ms"),
+                "frac_conv1x1_hbm": _get(roof, "frac_conv1x1_hbm"), "conv1x1_ms": _get(roof, "conv1x1_ms"),
+                "exact_fps": _get(exact, "value"), "steady_fps": _get(steady, "value"), "one_lane_fps": _get(one_lane, "value"),
+                "train_ms_per_step": _get(train, "ms_per_step"), "train_frac": tr_roof.get("frac"),
+                "parity_frames": _get(parity_line, "frames"), "argmax_mismatches": _get(parity_line, "argmax_mismatches"),
+                "argmax_mismatches_outside_rounding": _get(parity_line, "argmax_mismatches_outside_rounding"),
+                "max_joint_err_cm": _get(parity_line, "max_joint_err_cm"),
+                "cfg2_fps": _get(cfg_legs, "config2_heatmap_4view", "value"), "cfg3_fps": _get(cfg_legs, "config3_heatmap_mvfex", "value"),
+                "train_fps": _get(train, "value"), "train_dominant_kernel": tr_roof.get("kernel"), "train_launches_per_step": _get(train, "launches_per_step"),
+                "argmax_compared": _get(parity_line, "argmax_compared"), "valid_mask_mismatches": _get(parity_line, "valid_mask_mismatches"),
+                "argmax_mismatches_fp64_sides_with_hip": _get(parity_line, "argmax_mismatches_fp64_sides_with_hip"),
+                "top2_gap_below_1e-5": _get(parity_line, "top2_gap_below_1e-5"),
+                "all_kernels_ms_per_step": _get(roof, "all_kernels_ms_per_step"), "launches_per_forward": len(prof) if rank == 0 else None,
+            }
+            if roof is not None:
+                head = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic")
+                line["roofline"] = {**{k: roof[k] for k in head if k in roof}, **scal, **{k: v for k, v in roof.items() if k not in head and k not in scal}}
+            line.update(scal)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

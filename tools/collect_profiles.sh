@@ -6,9 +6,9 @@ tag=$1
 commit=${2:-unknown}
 out=gpurun_out/prof_$tag
 mkdir -p $out
-CMD="python3 bench.py --steps 5 --warmup 2 --steady-steps 0 --no-graph --no-cpu-baseline --no-train --no-configs"
+CMD="python3 bench.py --full --steps 5 --warmup 2 --steady-steps 0 --no-graph --no-cpu-baseline --no-train --no-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $CMD > $out/stats.log 2>&1
-PM="python3 bench.py --steps 2 --warmup 1 --steady-steps 0 --no-graph --no-cpu-baseline --no-train --no-configs"
+PM="python3 bench.py --full --steps 2 --warmup 1 --steady-steps 0 --no-graph --no-cpu-baseline --no-train --no-configs"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -- $PM > $out/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/write -- $PM > $out/write.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $out/mfma -- $PM > $out/mfma.log 2>&1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MFMA utilisation of the conv kernel from a rocprofv3 PMC pass:
-    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d DIR -- python3 bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d DIR -- python3 bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline
     python tools/pmc_mfma_util.py DIR out.json
 SQ_VALU_MFMA_BUSY_CYCLES counts cycles per SIMD (64 per v_mfma_f32_32x32x2_f32, 32 per v_mfma_f32_32x32x16_bf16), summed over the chip's
 1024 SIMDs; conv_igemm_bf16x3 = the launches of conv_igemm_x6_kernel (split-bf16 operands);

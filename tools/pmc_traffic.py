@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Reduce two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs as MI355X_MICROARCH.md prescribes) of
-`python3 bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline` into HBM bytes per launch of the conv kernel.
+`python3 bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline` into HBM bytes per launch of the conv kernel.
     python tools/pmc_traffic.py <fetch_dir> <write_dir> <out.json> [batch] [forwards] [commit]
 `forwards` = forwards the profiled command runs (12 for the command above: first + warm-up + 2 timed + the instrumented one + 7 of the
 from-raw-frames leg) -> launches_per_forward, which bench.py compares with its own run before it reports the figure.
@@ -42,6 +42,6 @@ x6 = entry("conv_x6", "conv_igemm_x6 / x6p / tap / tap2 / conv_pw_x6 kernels, th
 f32 = entry("conv", "conv_igemm_kernel (egr_conv2d_nhwc_f32, fp32-matrix-core launches)")
 main = h2 or x6 or f32
 out = {"batch": batch, "forwards_profiled": forwards, "commit": commit, **main, "by_format": {"f16x2": h2, "bf16x3": x6, "f32": f32},
-       "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-train"}
+       "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-train"}
 json.dump(out, open(sys.argv[3], "w"), indent=1)
 print(json.dumps(out))

@@ -3,7 +3,7 @@
 var=$1; shift
 mkdir -p gpurun_out
 for v in "$@"; do
-  env $var=$v python bench.py --no-train --no-cpu-baseline --no-configs 2>/dev/null | python -c "
+  env $var=$v python bench.py --full --no-train --no-cpu-baseline --no-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernel_ms']

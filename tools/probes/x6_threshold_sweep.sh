@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for cfg in "8192 4e9" "4096 2e9" "4096 1e9" "2048 1e9" "2048 5e8" "8192 4e9"; do
   set -- $cfg
-  EGR_X6_MIN_ROWS=$1 EGR_X6_MIN_FLOPS=$2 python bench.py --no-train --no-cpu-baseline --no-configs 2>/dev/null | python -c "
+  EGR_X6_MIN_ROWS=$1 EGR_X6_MIN_FLOPS=$2 python bench.py --full --no-train --no-cpu-baseline --no-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernel_ms']
