@@ -195,6 +195,10 @@ class State:
 
     def __init__(self, device, share: Optional["State"] = None):
         self.device = device
+        # the policy fields the packs below are made under (weight format, fp16 images of the fused layers, abs-max arena): _state()
+        # rebuilds the state when a forward runs under another policy, e.g. `with hip.use_policy(hip.POLICY.exact()):` on a module
+        # that was forwarded under the default before
+        self.policy_key = share.policy_key if share is not None else hip.policy().pack_key()
         self.packs: Dict[object, object] = share.packs if share is not None else {}
         self.workspace = torch.empty(_WORKSPACE_FLOATS, device=device, dtype=torch.float32)
         # abs-max records of the forward's activations (hip.AmaxArena): the pre-scales of the fp16-scheme launches come from them
@@ -280,7 +284,7 @@ GENERATION = [0]
 
 def _state(mod: nn.Module, device) -> State:
     st = mod.__dict__.get("_egr_state")
-    if st is None or st.device != device:
+    if st is None or st.device != device or st.policy_key != hip.policy().pack_key():
         st = State(device)
         GENERATION[0] += 1
         mod.__dict__["_egr_state"] = st
@@ -499,6 +503,7 @@ def _basic_block(st: State, blks, x: Img, out: Optional[Img] = None) -> Img:
 # EGR_STEM_POOL=0 keeps the two launches.
 STEM_POOL = os.environ.get("EGR_STEM_POOL", "1") != "0"
 # The stem on the bf16 matrix cores (egr_stem_conv7x7_x6_f32: split-bf16 operands like the other convolutions); EGR_STEM_X6=0: fp32 MFMA.
+# The "f32" weight format (fp32 matrix cores everywhere) takes the fp32 stem as well.
 STEM_X6 = os.environ.get("EGR_STEM_X6", "1") != "0"
 
 
@@ -510,7 +515,7 @@ def run_backbone(st: State, encs, img: torch.Tensor, view0: int, nviews: int, fe
     trunks, necks = [e.backbone for e in encs], [e.neck for e in encs]
     t0, n0 = trunks[0], necks[0]
     wp, sc, sh = st.get(t0.layer_s2, lambda: _pack_stems(trunks))
-    if STEM_X6 and img.shape[3] % 32 == 0 and img.shape[4] % 64 == 0:     # the split kernel's tile is 16 x 32 output pixels (fp32 kernel: 8 x 32)
+    if STEM_X6 and hip.policy().w_format != "f32" and img.shape[3] % 32 == 0 and img.shape[4] % 64 == 0:     # the split kernel's tile is 16 x 32 output pixels (fp32 kernel: 8 x 32)
         if hip.policy().w_format == "f16x2":       # the fp16 scheme (per-tile pre-scale of the input patch)
             wh2, wds = st.get((id(t0.layer_s2), "wh2"), lambda: hip.pack_stem_wh2(wp))
             x = hip.stem_x6(img, view0, nviews, wh2, sc, sh, groups=G, pool=STEM_POOL, w_descale=wds,
@@ -804,7 +809,8 @@ def _pack_refiners(rs) -> PRefiners:
 
 # tests only: a dict here receives the refiners' intermediates of the next forward - "query" (G, B, J, C) behind fc_query, "post_norm"
 # (G, B, J, C) behind the transformer layer + post_norm, "head_sum" (G*B, h, w, C) = head offset + own-view projection (NHWC) - the
-# tensors tests/golden/mvfex_mid_s*.npz pin against the reference (heatmap_mvf_ex.py:665, 699-706, 715)
+# tensors tests/golden/mvfex_mid_s*.npz pin against the reference (heatmap_mvf_ex.py:665, 699-706, 715) - and the feature maps
+# "feat_init" / "feat_refined" (B, V, C, H, W) of the heat-map estimator
 CAPTURE = None
 
 
@@ -902,6 +908,8 @@ def _mvfex(mod, img: torch.Tensor, heatmap_for_anchor=None):
     feat_ref = torch.empty_like(feat_all)
     hm_ref = torch.empty_like(hm_init)
     _run_refiners(st, mod.refiners(), B, V, hm_init, feat_all, s32_all, anchors, valid, feat_ref, hm_ref)
+    if CAPTURE is not None:
+        CAPTURE.update(feat_init=_vb_view(feat_all, V, B).clone(), feat_refined=_vb_view(feat_ref, V, B).clone())
     aux = {"anchors_2d": anchors, "maxvals": maxvals, "anchors_valid": valid, "argmax_idx": index}
     return hm_init, hm_ref, feat_all, feat_ref, aux
 

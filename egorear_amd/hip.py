@@ -77,6 +77,11 @@ class LaunchPolicy:
     def replace(self, **kw) -> "LaunchPolicy":
         return dataclasses.replace(self, **kw)
 
+    def pack_key(self) -> tuple:
+        """The fields that shape packed weights and abs-max arenas (engine.State, train.PackCache): packs made under one key are not
+        valid under another."""
+        return (self.w_format, self.h2, self.layer_h2)
+
     def exact(self) -> "LaunchPolicy":
         """The exact-operand arithmetic (EGR_W_FORMAT=bf16x3): three bf16 planes, six products, fused layers on the fp32 matrix cores."""
         return self.replace(w_format="bf16x3", h2=False, layer_h2=False)
@@ -1306,7 +1311,8 @@ def joint_layer(x: torch.Tensor, g: torch.Tensor, e: Optional[torch.Tensor], sig
             h0._egr_amax = rec
         head["out"] = h0
     flops = 2.0 * groups * B * (J * V * (Cdim * 128 + Cdim * Cdim) + J * (V * Cdim * Cdim + 3 * Cdim * Cdim + Cdim * Cdim + 2 * 512 * Cdim))
-    _launch("egr_joint_layer_f32", lib.egr_joint_layer_f32, C.byref(d), _stream(), flops=flops)
+    _launch("egr_joint_layer_f32", lib.egr_joint_layer_f32, C.byref(d), _stream(), flops=flops,
+            tag=f"{'h2' if packed == 2 else 'plain'} G{groups} B{B} J{J} C{Cdim}" if PROFILE is not None else "")
     return x_out, ol_out, xn, pred
 
 

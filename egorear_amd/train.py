@@ -105,6 +105,7 @@ class PackCache:
 
     def __init__(self, device):
         self.dev = device
+        self.policy_key = hip.policy().pack_key()     # operand images and the abs-max arena follow it (checked by _get_cache)
         self.packs: Dict[object, TPack] = {}
         self.table = repack.RepackTable(device)
         self.back = repack.RepackTable(device)    # BatchNorm running statistics: stacked buffers -> the modules' own, end of the forward
@@ -183,6 +184,11 @@ def _get_cache(net: nn.Module, device) -> PackCache:
     if c is None or c.dev != device or not c.valid():
         c = PackCache(device)
         net.__dict__["_egr_pack_cache"] = c
+    elif c.policy_key != hip.policy().pack_key():
+        # (a captured step holds pointers into this cache: it is not rebuilt behind the caller's back)
+        raise RuntimeError(f"egorear_amd.train: the module's operand cache was built under the launch policy {c.policy_key} "
+                           f"(w_format, h2, layer_h2) and is used under {hip.policy().pack_key()}; drop it first "
+                           "(del net.__dict__['_egr_pack_cache']) or train under the policy it was built under")
     return c
 
 

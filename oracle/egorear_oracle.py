@@ -151,7 +151,7 @@ def get_max_preds(heatmaps: torch.Tensor, threshold: float = 0.5, normalize: boo
     additionally for the parity tests, the raw int64 flat index (N,J)."""
     N, J, H, W = heatmaps.shape
     maxvals, idx = torch.max(heatmaps.reshape(N, J, -1), dim=2, keepdim=True)
-    preds = torch.tile(idx, (1, 1, 2)).float()
+    preds = torch.tile(idx, (1, 1, 2)).to(heatmaps.dtype if heatmaps.is_floating_point() else torch.float32)   # (float64 run: stays float64)
     preds[:, :, 0] = preds[:, :, 0] % W
     preds[:, :, 1] = preds[:, :, 1] // W
     if normalize:

@@ -52,4 +52,4 @@ def test_512_frames_at_the_benchmarked_arithmetic_vs_the_cpu_oracle(calib_dir):
         assert d["oracle_gap"] <= census.ROUNDING_GAP and "fp64_sides_with" in d, d
     assert acc["valid_mask_mismatches"] == 0, acc
     assert acc["max_joint_err_cm"] < 1e-3, acc
-    assert acc["max_heatmap_err"] < 1e-4, acc
+    assert acc["max_heatmap_err"] < 1e-5, acc           # (this sample: 3.0e-6; profiles/r07_referee_512.json: 3.8e-6; the 2048-frame run: 4.3e-6)

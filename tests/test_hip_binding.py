@@ -327,3 +327,19 @@ def test_launch_policy_from_environment_and_overrides():
         assert hip.POLICY.x6_min_rows == 123 and hip.policy().x6_min_rows == 123
     finally:
         hip.X6_MIN_ROWS = saved
+
+
+def test_train_pack_cache_refuses_another_policy():
+    """train.PackCache is made under one launch policy (operand images, abs-max arena): used under another it raises instead of running
+    a mixed arithmetic - no GPU involved (a stand-in cache with the recorded key)."""
+    import types
+    import torch.nn as nn
+    from egorear_amd import hip, train
+    net = nn.Linear(2, 2)
+    c = types.SimpleNamespace(dev="dev", valid=lambda: True, policy_key=hip.policy().pack_key())
+    net.__dict__["_egr_pack_cache"] = c
+    assert train._get_cache(net, "dev") is c
+    with hip.use_policy(hip.POLICY.exact()):
+        with pytest.raises(RuntimeError, match="launch policy"):
+            train._get_cache(net, "dev")
+    assert hip.POLICY.exact().pack_key() == ("bf16x3", False, False) and hip.LaunchPolicy().pack_key() == ("f16x2", True, True)
