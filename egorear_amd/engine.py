@@ -56,14 +56,14 @@ class PConv:
 W6_MAX_ELEMS = 1 << 24
 
 
-def _w_operand(w: Optional[torch.Tensor], h2: bool = True):
-    """h2=False: no fp16 companion image (the training step: its launches carry no abs-max records, and its images are re-split
-    after every update)."""
+def _w_operand(w: Optional[torch.Tensor]):
+    """The weight operand under the active policy: w itself ("f32", or a shape the split kernels do not take), its bf16x3 image,
+    and for "f16x2" that image with its fp16 companion."""
     fmt = hip.policy().w_format
     if w is None or fmt not in ("bf16x3", "f16x2") or not w.is_cuda or w.shape[-1] % 32 != 0 or w.shape[-2] * w.shape[-1] > W6_MAX_ELEMS:
         return w
     w6 = hip.pack_w6(w)
-    return hip.add_wh2(w6) if (h2 and fmt == "f16x2") else w6
+    return hip.add_wh2(w6) if fmt == "f16x2" else w6
 
 
 def _npad(cout: int) -> int:
@@ -499,14 +499,6 @@ def _basic_block(st: State, blks, x: Img, out: Optional[Img] = None) -> Img:
     return conv(st, y, p2, ACT_RELU, res=identity, res_mode=RES_BEFORE_ACT, out=out)
 
 
-# Stem conv + BatchNorm + ReLU + MaxPool2d(3, 2, 1) in one pass (egr_stem_conv7x7_pool_f32, bit-identical to the two kernels);
-# EGR_STEM_POOL=0 keeps the two launches.
-STEM_POOL = os.environ.get("EGR_STEM_POOL", "1") != "0"
-# The stem on the bf16 matrix cores (egr_stem_conv7x7_x6_f32: split-bf16 operands like the other convolutions); EGR_STEM_X6=0: fp32 MFMA.
-# The "f32" weight format (fp32 matrix cores everywhere) takes the fp32 stem as well.
-STEM_X6 = os.environ.get("EGR_STEM_X6", "1") != "0"
-
-
 def run_backbone(st: State, encs, img: torch.Tensor, view0: int, nviews: int, feat_out: Img, s32_out: Optional[Img] = None):
     """ResNet-18 trunk + FPN (resnet.py:43-74,121-137) of len(encs) encoders in grouped launches: encoder g processes
     views [view0 + g*nviews, view0 + (g+1)*nviews).  Writes the stride-4 features into `feat_out`
@@ -515,21 +507,18 @@ def run_backbone(st: State, encs, img: torch.Tensor, view0: int, nviews: int, fe
     trunks, necks = [e.backbone for e in encs], [e.neck for e in encs]
     t0, n0 = trunks[0], necks[0]
     wp, sc, sh = st.get(t0.layer_s2, lambda: _pack_stems(trunks))
-    if STEM_X6 and hip.policy().w_format != "f32" and img.shape[3] % 32 == 0 and img.shape[4] % 64 == 0:     # the split kernel's tile is 16 x 32 output pixels (fp32 kernel: 8 x 32)
+    # stem conv + BatchNorm + ReLU + MaxPool2d(3, 2, 1) of layer_s4 in one pass: on the bf16 matrix cores (split-bf16 operands like
+    # the other convolutions, egr_stem_conv7x7_x6_f32) when the shape fits its tile of 16 x 32 output pixels, else - and under the
+    # "f32" weight format - on fp32 MFMA (egr_stem_conv7x7_pool_f32, tile 8 x 32)
+    if hip.policy().w_format != "f32" and img.shape[3] % 32 == 0 and img.shape[4] % 64 == 0:
         if hip.policy().w_format == "f16x2":       # the fp16 scheme (per-tile pre-scale of the input patch)
             wh2, wds = st.get((id(t0.layer_s2), "wh2"), lambda: hip.pack_stem_wh2(wp))
-            x = hip.stem_x6(img, view0, nviews, wh2, sc, sh, groups=G, pool=STEM_POOL, w_descale=wds,
-                            amax_out=st.new_amax() if STEM_POOL else None)
+            x = hip.stem_x6(img, view0, nviews, wh2, sc, sh, groups=G, pool=True, w_descale=wds, amax_out=st.new_amax())
         else:
             w6 = st.get((id(t0.layer_s2), "w6"), lambda: hip.pack_stem_w6(wp))
-            x = hip.stem_x6(img, view0, nviews, w6, sc, sh, groups=G, pool=STEM_POOL,     # layer_s2 (+ the max-pool of layer_s4 in the same pass)
-                            amax_out=st.new_amax() if STEM_POOL else None)
-    elif STEM_POOL:
-        x = hip.stem_pool(img, view0, nviews, wp, sc, sh, groups=G)
+            x = hip.stem_x6(img, view0, nviews, w6, sc, sh, groups=G, pool=True, amax_out=st.new_amax())
     else:
-        x = hip.stem(img, view0, nviews, wp, sc, sh, groups=G)
-    if not STEM_POOL:
-        x = hip.maxpool(x, 3, 2, 1)
+        x = hip.stem_pool(img, view0, nviews, wp, sc, sh, groups=G)
     pyramid = []
     stages = [(t.layer_s4[1], t.layer_s8, t.layer_s16, t.layer_s32) for t in trunks]
     for si in range(4):

@@ -826,16 +826,6 @@ def conv1x1_chain(x: Img, w1, w2, cmid: int, cout: int, *, shift1=None, shift2=N
     return full
 
 
-def wgrad_is_split(x: Img, dy: Img, kh: int, kw: int, groups: int = 1) -> bool:
-    """Whether conv2d_wgrad would run this problem on the split kernels (the size rule of egr_conv2d_wgrad_f32, or the forced mode)."""
-    if not policy().wgrad_x6:
-        return False
-    if policy().wgrad_force:
-        return True
-    M = (x.n // groups) * dy.h * dy.w
-    return M >= 1024 and 2.0 * M * dy.c * kh * kw * x.c * groups >= 4e9
-
-
 def wgrad_records(x: Img, dy: Img, amax_arena: Optional["AmaxArena"]) -> None:
     """Abs-max records for the operands of a split weight-gradient launch that carry none (one read each), on the current stream."""
     if not policy().h2 or amax_arena is None:

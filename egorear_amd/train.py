@@ -23,14 +23,13 @@ from __future__ import annotations
 
 import contextlib
 import math
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import engine, hip
+from . import hip
 from . import hip_train as T
 from . import repack
 from .engine import _npad, _pad_rows, _pad_vec, _rows
@@ -39,36 +38,9 @@ from .hip import ACT_NONE, ACT_RELU, RES_BEFORE_ACT, RES_NONE, Img, NMap
 _WS_FLOATS = 72 << 20   # conv split-K / wgrad slab workspace (288 MB: one slab of mlp_pred.0's 2048 x 32768 gradient)
 
 
-# The fp16 scheme in the training step: forward and data-gradient launches above the split threshold take the two-plane
-# fp16 images of their weight operands; their inputs' abs-max records come from the producing conv launch, or from one extra read
-# (hip.conv2d's amax_arena).  EGR_TRAIN_H2=0 keeps the step on the bf16 scheme.
-TRAIN_H2 = os.environ.get("EGR_TRAIN_H2", "1") != "0"
-# Records of the BatchNorm outputs / gradients as BOUNDS from the batch extremes (hip_train.bn_train / bn_backward) instead of one read
-# of the tensor each (EGR_TRAIN_BOUNDS=0: the reads)
-TRAIN_BOUNDS = os.environ.get("EGR_TRAIN_BOUNDS", "1") != "0"
-# BatchNorm statistics of a conv output taken in the conv's epilogue (egr_conv_aux.bn_partials) instead of by a pass over the tensor
-BN_IN_CONV = os.environ.get("EGR_TRAIN_BN_IN_CONV", "1") != "0"
-
-
-# Weight gradients on a second stream (EGR_TRAIN_SIDE_STREAM=1; off by default): they depend only on a layer's input and output gradient
-# and nothing in the reverse pass waits for them before the parameter gradients are flushed, so they can be forked off the main stream
-# (own split workspace) and joined in finish_param_grads; a captured step records the fork / join as graph dependencies.  Measured
-# SLOWER (batch 32: 34.1 against 32.1 ms per step): the large weight-gradient and data-gradient launches of the CNN stages each fill
-# the chip, so running them side by side only makes them share CUs and L2 (conv 12.7 -> 16.0 ms, weight gradients 7.6 -> 12.2 ms of
-# kernel time), and the small latency-bound launches of the heads sit in a different phase of the reverse pass than the large ones.
-# Forking only the small launches ("small") is no better (33.7 ms): the replay of a graph with ~100 cross-stream edges costs the host
-# 21 ms per step and the device follows it.
-WGRAD_DIRECT = os.environ.get("EGR_TRAIN_WGRAD_DIRECT", "1") != "0"   # aligned single Linear layers: the weight gradient lands in the flat gradient buffer itself
-STEM_FUSED = os.environ.get("EGR_TRAIN_STEM_FUSED", "1") != "0"   # the stem's BatchNorm + ReLU + max-pool as one forward / one reverse launch set
-OVERLAP = os.environ.get("EGR_TRAIN_OVERLAP", "1") != "0"       # the leaves of the reverse pass on a second stream (Step.backward)
-# which parts (bits): 1 = forward branches (own-view projection, refined heads), 2 = the detached heads' reverse pass, 4 = the refiners' reverse pass
-# (measured and removed: the main stream's ~50 small weight gradients forked onto the side stream one by one - 25.4-25.7 -> 27.2-27.4 ms: every
-# cross-stream edge of a hipGraph costs more than the 10-us launch it takes off the chain; the lifting head's ~30 PARKED and handed over as one
-# batch at its stage marker - 26.3 ms: small launches queued on the side stream crawl beside the encoders' persistent convolutions and
-# hold up the refiners' reverse pass behind them, the final join then waits for the side stream)
-OVERLAP_PARTS = int(os.environ.get("EGR_TRAIN_OVERLAP_PARTS", "7"))
-SIDE_WGRAD = os.environ.get("EGR_TRAIN_SIDE_STREAM", "0")          # "0" | "small" (only launches below the split threshold) | "1" (all)
-SIDE_WGRAD = SIDE_WGRAD if SIDE_WGRAD in ("small", "1") else ""
+# Schedule switches: plain attributes that tools/train_bench.py, bench.py and two tests flip for their one-stream / unpacked references.
+WGRAD_DIRECT = True     # aligned single Linear layers: the weight gradient lands in the flat gradient buffer itself (Step._wgrad)
+OVERLAP = True          # the leaves of the reverse pass on a second stream (Step.backward; other schedules measured and dropped: DESIGN.md 9)
 
 
 def _conv2d(*a, **k):
@@ -113,8 +85,10 @@ class PackCache:
         self.images: List = []               # hip.W6 operands re-split from their fp32 matrices after every refresh
         self._w6_table, self._w6_key = None, None
         self._h2_table, self._h2_key = None, None
-        # abs-max records of one step's activations and gradients (the graph of a captured step holds pointers into it)
-        self.amax = hip.AmaxArena(device, records=1024) if (TRAIN_H2 and hip.policy().h2 and hip.policy().w_format == "f16x2") else None
+        # abs-max records of one step's activations and gradients, for the fp16 scheme: forward and data-gradient
+        # launches above the split threshold take the two-plane fp16 images of their weight operands (the graph of a captured step
+        # holds pointers into it)
+        self.amax = hip.AmaxArena(device, records=1024) if (hip.policy().h2 and hip.policy().w_format == "f16x2") else None
         self.sources: Dict[int, tuple] = {}  # id(param) -> (param, data_ptr)
         self.ready = False
 
@@ -274,7 +248,7 @@ def make_pack(cache: PackCache, key, wparts, bparts, name_of, kh: int = 1, kw: i
     p.w6 = p.wt6 = None
     for attr, src in (("w6", p.w), ("wt6", p.wt)):
         if src is not None:
-            op = _w_operand(src, h2=TRAIN_H2)
+            op = _w_operand(src)
             if isinstance(op, hip.W6):
                 setattr(p, attr, op)
                 cache.images.append(op)
@@ -284,65 +258,76 @@ def make_pack(cache: PackCache, key, wparts, bparts, name_of, kh: int = 1, kw: i
 
 # --------------------------------------------------------------------------- gradient store + tape
 
+def _wait(waiter, producer):
+    """waiter.wait_stream(producer) between two different streams: a stream made to wait on itself is a scheduling bug (round 6's
+    crash inside hipStreamEndCapture was one)."""
+    assert waiter != producer, "egorear_amd.train: a stream made to wait on itself"
+    waiter.wait_stream(producer)
+
+
+def _other_stream(device) -> torch.cuda.Stream:
+    """A stream other than the current one.  torch hands out pooled streams round-robin, so a new one can be the stream a graph
+    capture runs on."""
+    s = torch.cuda.Stream(device=device)
+    return s if s != torch.cuda.current_stream(device) else torch.cuda.Stream(device=device)
+
+
 class _Grads:
     """Gradients of forward tensors, keyed by the identity of the tensor object the forward produced."""
 
     def __init__(self):
         self.g: Dict[int, torch.Tensor] = {}
         self.gm: Dict[int, torch.Tensor] = {}   # contributions to post-ReLU tensors that already carry the [y > 0] mask
-        # Round 6: parts of the reverse pass run on a second stream (Step.backward).  When `track` is on, every stored gradient carries
-        # the stream of the launch that produced it; a closure that takes it on ANOTHER stream first makes its stream wait for what
-        # the producer's stream has been given so far (and tells the allocator about the second user) - gradient flow across streams
-        # is ordered by construction.  (One event per stored gradient would be the finer tool; ending a hipGraph capture that holds
-        # a few hundred recorded-and-dropped events crashed inside hipStreamEndCapture, Stream.wait_stream is the proven path.)
+        # Round 6: parts of the reverse pass run on a second stream (Step.backward).  When `track` is on, every slot of the store
+        # remembers the stream of the launch that last wrote it; a closure that takes the gradient on ANOTHER stream first makes its
+        # stream wait for what the producer's stream has been given so far - gradient flow across streams is ordered by construction.
+        # (The capture crash inside hipStreamEndCapture that round 6 first blamed on per-gradient events and record_stream was a stream
+        # made to wait on itself by a side-stream branch of Step._wgrad, since removed; _wait refuses that pattern.)
         self.track = False
-        self.src: Dict[int, object] = {}        # id(gradient tensor) -> producing stream
+        self.src: Dict[tuple, object] = {}      # (masked store?, id(forward tensor)) -> stream that produced the stored gradient
         self.hold: List = []
 
-    def _produced(self, g: torch.Tensor):
+    def _set(self, store: dict, k: int, g: torch.Tensor):
+        store[k] = g
         if self.track:
-            self.src[id(g)] = torch.cuda.current_stream(g.device)
+            self.src[(store is self.gm, k)] = torch.cuda.current_stream(g.device)
 
-    def _taken(self, g: Optional[torch.Tensor], drop: bool):
+    def _take(self, store: dict, k: int, drop: bool) -> Optional[torch.Tensor]:
+        g = store.pop(k, None) if drop else store.get(k)
         if self.track and g is not None:
-            st = self.src.pop(id(g), None) if drop else self.src.get(id(g))
+            st = self.src.pop((store is self.gm, k), None) if drop else self.src.get((store is self.gm, k))
             if st is not None:
                 cur = torch.cuda.current_stream(g.device)
                 if st != cur:
-                    cur.wait_stream(st)
+                    _wait(cur, st)
                     # the allocator must not hand the block back to the producer's stream while this stream still reads it: the
-                    # tensor lives to the end of the step (every stream is joined by then) - Tensor.record_stream inside a hipGraph
-                    # capture crashed hipStreamEndCapture on this stack
+                    # tensor lives to the end of the step (every stream is joined by then) - kept instead of Tensor.record_stream,
+                    # which would change what a captured step's memory pool holds
                     self.hold.append(g)
         return g
 
     def add_masked(self, t: torch.Tensor, g: torch.Tensor):
-        k = id(t)
-        old = self._taken(self.gm.get(k), True)
-        self.gm[k] = g if old is None else T.add(old, g)
-        self._produced(self.gm[k])
+        old = self._take(self.gm, id(t), True)
+        self._set(self.gm, id(t), g if old is None else T.add(old, g))
 
     def pop_masked(self, t: torch.Tensor) -> Optional[torch.Tensor]:
-        return self._taken(self.gm.pop(id(t), None), True)
+        return self._take(self.gm, id(t), True)
 
     def add(self, t: torch.Tensor, g: torch.Tensor):
         if g.shape != t.shape:
             g = g.view(t.shape)
-        k = id(t)
-        old = self._taken(self.g.get(k), True)
-        self.g[k] = g if old is None else T.add(old, g)
-        self._produced(self.g[k])
+        old = self._take(self.g, id(t), True)
+        self._set(self.g, id(t), g if old is None else T.add(old, g))
 
     def put(self, t: torch.Tensor, g: torch.Tensor):
-        """Store g as THE gradient of t (the caller has folded the previous value in)."""
-        self.g[id(t)] = g
-        self._produced(g)
+        """Store g as THE gradient of t (the caller has folded the previous value in, or edited the peeked one in place)."""
+        self._set(self.g, id(t), g)
 
     def pop(self, t: torch.Tensor) -> Optional[torch.Tensor]:
-        return self._taken(self.g.pop(id(t), None), True)
+        return self._take(self.g, id(t), True)
 
     def peek(self, t: torch.Tensor) -> Optional[torch.Tensor]:
-        return self._taken(self.g.get(id(t)), False)
+        return self._take(self.g, id(t), False)
 
 
 class _OnSide:
@@ -384,23 +369,25 @@ class Step:
         if self.amax is not None:
             self.amax.begin()      # (one fill launch: every record of the step starts from zero)
         T.set_arena(self.amax)     # element-wise launches bound their outputs by their inputs' records
-        self.side, self.ws_side, self._forked = None, None, False
-        # ---- two-stream step (round 6, EGR_TRAIN_OVERLAP): forward_train switches it on for the config-5 graph, whose detached heat-map
+        self.side, self.ws_side = None, None
+        # ---- two-stream step (round 6, train.OVERLAP): forward_train switches it on for the config-5 graph, whose detached heat-map
         # heads and refiners are LEAVES of the reverse pass (they feed parameter gradients only): they run on the side stream under the
         # lifting head's / the encoders' launches.  One process only: the staged multi-process capture cuts the tape at stage markers.
         self.allow_overlap = False
         self._on_side = False      # launches issued now go to the side stream (its split-K workspace is ws_side)
-        self.bwd_side = False      # closures recorded now run on the side stream in the reverse pass ...
+        self.bwd_side = False      # closures recorded now run on the side stream in the reverse pass (Step.leaf) ...
         self.bwd_early = False     # ... and ahead of everything else (seed-only leaves)
         self._side_dirty = False   # the side stream holds work the main stream has not waited for
-        if SIDE_WGRAD or OVERLAP:
+        if OVERLAP:
             ss = net.__dict__.get("_egr_side")
             if ss is None or ss[1].device != device:
-                ss = (torch.cuda.Stream(device=device), torch.empty(_WS_FLOATS, device=device, dtype=torch.float32))
-                net.__dict__["_egr_side"] = ss
+                ss = (_other_stream(device), torch.empty(_WS_FLOATS, device=device, dtype=torch.float32))
+            elif ss[0] == torch.cuda.current_stream(device):      # (this step is captured on the side stream of earlier ones)
+                ss = (_other_stream(device), ss[1])
+            net.__dict__["_egr_side"] = ss
             self.side, self.ws_side = ss
         self.relu_out = set()  # ids of tensors produced by a fused ReLU: conv data gradients into them apply the mask themselves
-        self.record = True     # False: evaluate without taping (constant sub-graphs)
+        self.record = True     # False: evaluate without taping (constant sub-graphs; Step.untaped)
         self.bn_dirty = False
         self.bn_mods: List = []
         self.loss_terms = None
@@ -421,22 +408,36 @@ class Step:
         return self.ws_side if self._on_side else self._ws_main
 
     def overlap(self) -> bool:
-        return bool(OVERLAP and not SIDE_WGRAD and self.allow_overlap and self.stage_hook is None and self.side is not None)
+        return bool(OVERLAP and self.allow_overlap and self.stage_hook is None and self.side is not None)
 
     def _rec(self, fn):
-        """Record a reverse-pass closure (on the side stream when the forward marked this section as a leaf: bwd_side)."""
-        side = self.bwd_side and self.overlap() and (OVERLAP_PARTS & (2 if self.bwd_early else 4))
-        self.tape.append(_OnSide(fn, self.bwd_early) if side else fn)
+        """Record a reverse-pass closure (on the side stream when the forward marked this section as a leaf: Step.leaf)."""
+        self.tape.append(_OnSide(fn, self.bwd_early) if (self.bwd_side and self.overlap()) else fn)
 
     @contextlib.contextmanager
-    def side_branch(self):
-        """Forward: the block's launches go to the side stream, behind everything the main stream has been given so far; whoever
-        reads the results on the main stream calls join_side() first."""
-        if not (self.overlap() and OVERLAP_PARTS & 1):
+    def leaf(self, early: bool = False):
+        """Forward: the reverse-pass closures recorded in the block form a LEAF of the reverse pass (they feed parameter gradients only)
+        and run on the side stream in the two-stream step; early: a seed-only leaf, enqueued ahead of everything else."""
+        saved = self.bwd_side, self.bwd_early
+        self.bwd_side, self.bwd_early = True, self.bwd_early or early
+        try:
             yield
-            return
-        main = torch.cuda.current_stream(self.dev)
-        self.side.wait_stream(main)
+        finally:
+            self.bwd_side, self.bwd_early = saved
+
+    @contextlib.contextmanager
+    def untaped(self):
+        """Forward: the block is evaluated without recording reverse-pass closures (a constant sub-graph)."""
+        saved, self.record = self.record, False
+        try:
+            yield
+        finally:
+            self.record = saved
+
+    @contextlib.contextmanager
+    def on_side(self):
+        """Launches issued in the block go to the side stream (with its split-K workspace); the main stream joins it later (join_side)."""
+        assert torch.cuda.current_stream(self.dev) != self.side, "egorear_amd.train: side-stream sections do not nest"
         self._on_side = True
         try:
             with torch.cuda.stream(self.side):
@@ -445,9 +446,20 @@ class Step:
             self._on_side = False
             self._side_dirty = True
 
+    @contextlib.contextmanager
+    def side_branch(self):
+        """Forward: the block's launches go to the side stream, behind everything the main stream has been given so far; whoever
+        reads the results on the main stream calls join_side() first."""
+        if not self.overlap():
+            yield
+            return
+        _wait(self.side, torch.cuda.current_stream(self.dev))
+        with self.on_side():
+            yield
+
     def join_side(self):
         if self._side_dirty:
-            torch.cuda.current_stream(self.dev).wait_stream(self.side)
+            _wait(torch.cuda.current_stream(self.dev), self.side)
             self._side_dirty = False
 
     # ---- bookkeeping
@@ -470,9 +482,6 @@ class Step:
 
     def finish_param_grads(self):
         self.join_side()          # the leaves of the reverse pass on the side stream: their slabs feed the table below
-        if self._forked:          # the weight gradients forked onto the side stream: their slabs feed the table below
-            torch.cuda.current_stream().wait_stream(self.side)
-            self._forked = False
         for name, g in self.pextra.items():       # gradients assembled in parameter space: through the same table (one launch for all)
             dst = self.gdst(name)
             if g.dtype == torch.float32 and g.is_contiguous() and dst.is_contiguous() and g.numel() == dst.numel():
@@ -495,25 +504,17 @@ class Step:
             self.tape.append(bwd)      # (a marker, never a leaf: plain entry - tests drive mark_stage / backward on a stand-in object)
 
     def backward(self):
-        side = getattr(self, "side", None)
-
-        def on_side(fn):
-            self._on_side = True
-            try:
-                with torch.cuda.stream(side):
-                    fn()
-            finally:
-                self._on_side = False
-                self._side_dirty = True
         # seed-only leaves first: every one of them starts by taking a loss seed out of the gradient store, which orders the side
         # stream behind the seed's launch (and through it behind the whole forward)
         for fn in reversed(self.tape):
             if isinstance(fn, _OnSide) and fn.early:
-                on_side(fn.fn)
+                with self.on_side():
+                    fn.fn()
         for fn in reversed(self.tape):
             if isinstance(fn, _OnSide):
                 if not fn.early:
-                    on_side(fn.fn)
+                    with self.on_side():
+                        fn.fn()
             else:
                 fn()
         self.tape = []
@@ -554,31 +555,16 @@ class Step:
     def _wgrad(self, p: TPack, x4: torch.Tensor, dz4: torch.Tensor, gx_rows: Optional[int] = None):
         """Weight / bias gradients of every group.  x4 (G*n, h, w, cin_pad), dz4 (G*n, ho, wo, cout_pad) dense."""
         xi, di = Img(x4), Img(dz4)
-        big = hip.wgrad_is_split(xi, di, p.kh, p.kw, p.groups)
         # a plain, unpadded single Linear / 1x1 conv: the packed gradient IS the parameter's layout - written straight into its place in
         # the flat gradient buffer, no unpack copy (mlp_pred.0: 268 MB read + 268 MB written by the step's repack launch)
         direct = None
         if (WGRAD_DIRECT and p.groups == 1 and len(p.wmeta[0]) == 1 and p.kh * p.kw == 1 and p.cin_pad == p.cin and p.cout_pad == p.cout
-                and p.wmeta[0][0][2] == 0 and p.wmeta[0][0][3] == p.cin and not SIDE_WGRAD):
+                and p.wmeta[0][0][2] == 0 and p.wmeta[0][0][3] == p.cin):
             dst = self.gdst(p.wmeta[0][0][0])
             if dst.is_contiguous() and dst.numel() == p.cout * p.cin and dst.data_ptr() % 16 == 0:
                 direct = dst.view(p.cout, p.cin)
-        if not SIDE_WGRAD or self.side is None or (big and SIDE_WGRAD == "small"):
-            dws, dbs = hip.conv2d_wgrad(xi, di, p.kh, p.kw, p.stride, p.pad, self.ws, want_bias=p.bmeta is not None, groups=p.groups,
-                                        amax_arena=self.amax, dw=direct)
-        else:
-            main = torch.cuda.current_stream()
-            if big:
-                hip.wgrad_records(xi, di, self.amax)      # on the main stream: the data-gradient launch of this layer reads dz's record there
-            self.side.wait_stream(main)
-            with torch.cuda.stream(self.side):
-                dws, dbs = hip.conv2d_wgrad(xi, di, p.kh, p.kw, p.stride, p.pad, self.ws_side, want_bias=p.bmeta is not None, groups=p.groups)
-            for t in (x4, dz4):
-                t.record_stream(self.side)
-            for t in (dws, dbs):
-                if t is not None:
-                    t.record_stream(main)
-            self._forked = True
+        dws, dbs = hip.conv2d_wgrad(xi, di, p.kh, p.kw, p.stride, p.pad, self.ws, want_bias=p.bmeta is not None, groups=p.groups,
+                                    amax_arena=self.amax, dw=direct)
         taps = p.kh * p.kw
         Kp = p.cin_pad * taps
         for g in range(p.groups):       # packed (rows, cin_pad/32, taps, 32) pieces -> OIHW (column slices) of the parameters' gradients
@@ -610,7 +596,7 @@ class Step:
         # supports it (raw dense output, cout % 64 == 0); the BatchNorm then only finalises the slabs (Step.bn)
         slabs = None
         kw_bn = {}
-        if stats and BN_IN_CONV and act == ACT_NONE and res is None and cw == p.cout and p.cout % 64 == 0 and p.bias is None:
+        if stats and act == ACT_NONE and res is None and cw == p.cout and p.cout % 64 == 0 and p.bias is None:
             slabs = []
             kw_bn = dict(bn_ws=self.bnws, bn_slabs=slabs)
         try:
@@ -672,7 +658,7 @@ class Step:
     # ---- BatchNorm (training mode), grouped ----------------------------------------------------------------------
     def bn(self, x: torch.Tensor, bns: Sequence[nn.BatchNorm2d], res: Optional[torch.Tensor] = None, relu: bool = True,
            pool: Optional[tuple] = None) -> torch.Tensor:
-        """pool = (k, stride, pad): the MaxPool2d that follows BatchNorm + ReLU evaluated in the same pass (the stem, STEM_FUSED): the
+        """pool = (k, stride, pad): the MaxPool2d that follows BatchNorm + ReLU evaluated in the same pass (the stem): the
         result is the pooled tensor; neither the normalised tensor nor the max-pool's scattered gradient is ever written."""
         G = len(bns)
         npk = norm_pack(self.cache, bns, True)
@@ -682,8 +668,8 @@ class Step:
         if slabs is not None:
             x._egr_bn_slabs = None
         y, ctx = T.bn_train(x, gamma, beta, rm, rv, G, self.bnws, res=res, relu=relu, momentum=b0.momentum, eps=b0.eps, slabs=slabs,
-                            amax_out=self.amax.new() if (self.amax is not None and TRAIN_BOUNDS) else None,
-                            want_extremes=self.amax is not None and TRAIN_BOUNDS,      # (the backward's bound needs max |xhat| even when y gets none)
+                            amax_out=self.amax.new() if self.amax is not None else None,
+                            want_extremes=self.amax is not None,      # (the backward's bound needs max |xhat| even when y gets none)
                             pool=pool)
         # nn.BatchNorm2d buffer side effects of a training forward: the running statistics go back to the modules' buffers in one launch
         # at the end of the forward, the counters are incremented there in one multi-tensor launch (flush_buffers)
@@ -700,17 +686,17 @@ class Step:
                 return
             if pool is not None:     # dy: gradient of the pooled tensor; the ReLU mask is recomputed from x inside the launch
                 dx, dgam, dbet, _ = T.bn_backward(ctx, dy, None, self.bnws,
-                                                  amax_dx=self.amax.new() if (self.amax is not None and TRAIN_BOUNDS) else None)
+                                                  amax_dx=self.amax.new() if self.amax is not None else None)
                 dz = None
             elif dzm is not None:      # (part of) the gradient arrived already masked: finish the sum, no mask inside the kernels
                 if dy is not None:
                     dzm = T.add(dzm, T.relu_bwd(dy, y))
                 dx, dgam, dbet, _ = T.bn_backward(ctx, dzm, None, self.bnws, want_dz=False,
-                                                  amax_dx=self.amax.new() if (self.amax is not None and TRAIN_BOUNDS) else None)
+                                                  amax_dx=self.amax.new() if self.amax is not None else None)
                 dz = dzm
             else:
                 dx, dgam, dbet, dz = T.bn_backward(ctx, dy, y if relu else None, self.bnws, want_dz=res is not None,
-                                                   amax_dx=self.amax.new() if (self.amax is not None and TRAIN_BOUNDS) else None)
+                                                   amax_dx=self.amax.new() if self.amax is not None else None)
             c_ = dgam.shape[1]
             for g, b in enumerate(bns):
                 self.gtable.add(repack.COPYPAD, dgam, self.gdst(self.name(b.weight)), 0, rows=c_, total=c_, src_off=g * c_)
@@ -897,10 +883,12 @@ def backbone_train(S: Step, encs, img: torch.Tensor, view0: int, nviews: int):
             S.cache.watch(w)
         tbl.run()
         S.cache.packs[key] = wp
-    # (split-bf16 launch like the other convolutions; the bank is re-split from the refreshed fp32 pack every step: one tiny launch)
-    # (with TRAIN_H2 in the fp16 scheme like the inference stem: per-tile pre-scale from the patch itself, no record needed)
-    if engine.STEM_X6 and H % 32 == 0 and W % 64 == 0:
-        if TRAIN_H2 and hip.policy().h2 and hip.policy().w_format == "f16x2":
+    # the inference stem's rule (engine.run_backbone): split-bf16 operands unless the policy is "f32" or the shape misses the tile, and
+    # in the fp16 scheme a per-tile pre-scale from the patch itself (no record needed); the bank is re-split from the refreshed fp32
+    # pack every step: one tiny launch
+    pol = hip.policy()
+    if pol.w_format != "f32" and H % 32 == 0 and W % 64 == 0:
+        if pol.h2 and pol.w_format == "f16x2":
             bank, wds = hip.pack_stem_wh2(wp)
             x = hip.stem_x6(img, view0, nviews, bank, None, None, groups=G, w_descale=wds).t
         else:
@@ -923,11 +911,8 @@ def backbone_train(S: Step, encs, img: torch.Tensor, view0: int, nviews: int):
     mk = mp.kernel_size if isinstance(mp.kernel_size, int) else mp.kernel_size[0]
     ms = mp.stride if isinstance(mp.stride, int) else mp.stride[0]
     mpad = mp.padding if isinstance(mp.padding, int) else mp.padding[0]
-    if STEM_FUSED:       # BatchNorm + ReLU + MaxPool2d in one pass, their reverse pass without the full-resolution y / dy (egr_bn_relu_maxpool_f32)
-        x = S.bn(x, [t.layer_s2[1] for t in trunks], relu=True, pool=(mk, ms, mpad))
-    else:
-        x = S.bn(x, [t.layer_s2[1] for t in trunks], relu=True)
-        x = S.maxpool(x, mk, ms, mpad)
+    # BatchNorm + ReLU + MaxPool2d in one pass, their reverse pass without the full-resolution y / dy (egr_bn_relu_maxpool_f32)
+    x = S.bn(x, [t.layer_s2[1] for t in trunks], relu=True, pool=(mk, ms, mpad))
     pyramid = []
     stages = [(t.layer_s4[1], t.layer_s8, t.layer_s16, t.layer_s32) for t in trunks]
     for si in range(4):
@@ -1097,7 +1082,8 @@ def layer_train(S: Step, L: _LayerPack, x: torch.Tensor, memory: torch.Tensor, a
     S._rec(bwd_sampling)
     S.keep.append((ol, g, e, sigma, a))
     # masked_fill(~valid) after output_proj: rows of invalid anchors are zero and pass no gradient.  Forward and gradient
-    # are masked in place (the gradient tensor is the fresh output of fuse_mlp's data-gradient launch, nobody else holds it).
+    # are masked in place (the gradient tensor is the fresh output of fuse_mlp's data-gradient launch, nobody else holds it);
+    # stored back, so that the store knows which stream edited it last.
     om = S.linear(a, L.out_proj)
     mask_all = rowmask.repeat(G) if G > 1 else rowmask
     T.rowmask_(om, mask_all)
@@ -1105,7 +1091,7 @@ def layer_train(S: Step, L: _LayerPack, x: torch.Tensor, memory: torch.Tensor, a
     def bwd_mask():
         d = S.G.peek(om)
         if d is not None:
-            T.rowmask_(d, mask_all)
+            S.G.put(om, T.rowmask_(d, mask_all))
     S._rec(bwd_mask)
     omv = om.view(G * B * J, V * C)
     S.alias(om, omv)
@@ -1169,10 +1155,8 @@ def refiners_train(S: Step, rs, B: int, V: int, hm_init: torch.Tensor, feat_all:
     S.mark_stage(1)
     # --- own-view projection: a constant in this configuration (`offset_pred + frame_feat.detach()`, :715) - evaluated without tape, and
     # (two-stream step) beside the token chain below: ~1 ms of convolutions under ~0.7 ms of small launches
-    S.record = False
-    with S.side_branch():
+    with S.untaped(), S.side_branch():
         ff = run_stack_train(S, [r.frame_feat_proj_layers for r in rs], feat_all, need_dx_first=False)
-    S.record = True
     # --- JQA query: heatmap_proj.0 reads the (B, V, J, hw) heat maps in place, group g = view g
     hp0 = S.pack([r.heatmap_proj[0] for r in rs], need_dx=hm_grad)
     hm_rows = Img(hm_init.view(B * V, J, 1, hw)[0::V])
@@ -1238,11 +1222,10 @@ def refiners_train(S: Step, rs, B: int, V: int, hm_init: torch.Tensor, feat_all:
     summed = S.add(off, None, b_const=ff)
     feat_ref = run_stack_train(S, [r.frame_feat_refined_proj_layers[0] for r in rs], summed)
     # the refined heads: forward beside whatever the caller runs next on the main stream (the lifting head's token chain; the caller
-    # joins before it reads hm_ref), reverse pass as a seed-only leaf when they see detached features
-    early, S.bwd_early = S.bwd_early, S.bwd_early or (S.bwd_side and detach_heatmap_feat)
-    with S.side_branch():
+    # joins before it reads hm_ref), reverse pass as a seed-only leaf when they see detached features inside the caller's leaf
+    seed_only = S.leaf(early=True) if (S.bwd_side and detach_heatmap_feat) else contextlib.nullcontext()
+    with seed_only, S.side_branch():
         heatmap_head_train(S, [r.conv_heatmap_layers[0] for r in rs], feat_ref, hm_ref, B, V, need_dx_first=not detach_heatmap_feat)
-    S.bwd_early = early
     return feat_ref
 
 
@@ -1330,15 +1313,13 @@ def forward_train(S: Step, net, img: torch.Tensor, ctm=None):
     feat_all, s32_all = backbone_train(S, [front.encoder, back.encoder], img, 0, 2)
     hm_init = torch.empty((B, V, J, H4, W4), device=dev, dtype=torch.float32)
     S.mark_stage(2)
-    S.bwd_side = S.bwd_early = True      # reverse pass: seed-only leaf
-    heatmap_head_train(S, [he.conv_heatmap_layers_stereo_front, he.conv_heatmap_layers_stereo_back], feat_all, hm_init, B, V)
-    S.bwd_side = S.bwd_early = False
+    with S.leaf(early=True):             # reverse pass: seed-only leaf
+        heatmap_head_train(S, [he.conv_heatmap_layers_stereo_front, he.conv_heatmap_layers_stereo_back], feat_all, hm_init, B, V)
     a, mv, vd, idx = hip.argmax_rows(hm_init, he.heatmap_threshold)
     anchors, valid = a.view(B, V, J, 2), vd.view(B, V, J)
     hm_ref = torch.empty_like(hm_init)
-    S.bwd_side = True                    # reverse pass: the refiners are a leaf behind d(feat_ref)
-    feat_ref = refiners_train(S, he.refiners(), B, V, hm_init, feat_all, s32_all, anchors, valid, hm_ref)
-    S.bwd_side = False
+    with S.leaf():                       # reverse pass: the refiners are a leaf behind d(feat_ref)
+        feat_ref = refiners_train(S, he.refiners(), B, V, hm_init, feat_all, s32_all, anchors, valid, hm_ref)
     preds, aux_p = pose3d_train(S, p3, feat_all, feat_ref, B, V, ctm)
     S.join_side()                        # the refined heads' forward ran beside the lifting head's: hm_ref is complete from here on
     aux = {"heatmap": {"anchors_2d": anchors, "anchors_valid": valid, "argmax_idx": idx.view(B, V, J), "maxvals": mv.view(B, V, J)},
@@ -1380,7 +1361,6 @@ def forward_backward(net, img, ctm, gt_pose, gt_heatmap):
     if not img.is_cuda:
         raise RuntimeError("egorear_amd.train: HIP device tensors only (no CPU path)")
     S = Step(net, img.device)
-    S.record = True
     with torch.no_grad():
         preds, hms, aux = forward_train(S, net, img, ctm)
         loss_and_seed(S, preds, hms, gt_pose, gt_heatmap)
@@ -1859,10 +1839,8 @@ def mvfex_heatmap_forward_train(S: Step, he, img: torch.Tensor):
     H4, W4 = img.shape[3] // 4, img.shape[4] // 4
     J = he.num_heatmap
     front, back = he.heatmap_estimator_stereo_front, he.heatmap_estimator_stereo_back
-    rec = S.record
-    S.record = False                     # `with torch.no_grad():` around the encoders (:267-268); BatchNorm still updates its buffers
-    feat_all, s32_all = backbone_train(S, [front.encoder, back.encoder], img, 0, 2)
-    S.record = rec
+    with S.untaped():                    # `with torch.no_grad():` around the encoders (:267-268); BatchNorm still updates its buffers
+        feat_all, s32_all = backbone_train(S, [front.encoder, back.encoder], img, 0, 2)
     hm_init = torch.empty((B, V, J, H4, W4), device=img.device, dtype=torch.float32)
     heatmap_head_train(S, [he.conv_heatmap_layers_stereo_front, he.conv_heatmap_layers_stereo_back], feat_all, hm_init, B, V)
     a, mv, vd, idx = hip.argmax_rows(hm_init, he.heatmap_threshold)

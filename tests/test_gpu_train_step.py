@@ -462,7 +462,7 @@ def test_two_stream_reverse_pass_gives_the_one_stream_gradients():
 
 
 def test_direct_weight_gradient_of_aligned_linears_equals_the_unpacked_copy():
-    """Round 6 (Step._wgrad, EGR_TRAIN_WGRAD_DIRECT): a plain, unpadded single Linear / 1x1 conv's weight gradient is written straight into
+    """Round 6 (Step._wgrad, train.WGRAD_DIRECT): a plain, unpadded single Linear / 1x1 conv's weight gradient is written straight into
     the parameter-shaped destination instead of a packed buffer that the step's repack launch copies - same launch, same values:
     bit-identical for every such tensor (mlp_pred.0's 2048 x 32768 matrix among them)."""
     from egorear_amd import configs, synth, train
