@@ -201,3 +201,193 @@ extern "C" int egr_gt_heatmap_f32(const double* joints, int32_t maps, double ima
                        image_size / (double)heatmap_size, heatmap_size, tmp_size, gauss, out);
     return egr_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Heat-map validation metrics: replaces `evaluate` of pl_wrappers/egoposeformer/heatmap.py:220-254 and
+// heatmap_mvf_ex.py:263-316 (get_max_preds: utils/loss.py:122-142) and `evaluate_heatmap` of pose_3d_mvf_ex.py:335-361, which
+// the reference runs as a Python loop with one device-to-host copy per sample.
+// Phase 1, one workgroup per (b, v, j) map: the ground truth is read once for all `sets` predictions; per set the three sums
+// {|p - g|, |p - g| where g > 0, (p - g)^2} are taken in fp64 (the launch is bound by the loads) and the first maximum is tracked
+// with the tie rule of argmax_kernel.  Reduction order is fixed: lane, wave butterfly, LDS over the four waves in wave order.
+// Phase 2, one workgroup per (set, view group): per sample the per-map partials are added in (view, joint) order, then the
+// samples' squared-error sums and the integer point distances go through the same fixed tree.  No atomics anywhere: two runs
+// give the same bits.
+namespace {
+
+constexpr int HM_MAXS = EGR_HM_MAX_SETS;
+constexpr int HM_MAXG = EGR_HM_MAX_GROUPS;
+
+struct hm_args {
+    const float* pred[HM_MAXS];
+    int32_t v0[HM_MAXG], v1[HM_MAXG];
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ void hm_take(float v, int i, float& best, int& bidx) {
+    if (v > best || bidx == 0x7fffffff) { best = v; bidx = i; }
+}
+
+__device__ __forceinline__ void hm_merge(float ov, int oi, float& best, int& bidx) {
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+}
+
+__global__ __launch_bounds__(256) void heatmap_partials_kernel(hm_args a, const float* gt, int sets, int maps, int hw, float thr,
+                                                               double* partials, int32_t* argmax, float* maxval, uint8_t* valid) {
+    const int map = blockIdx.x;
+    if (map >= maps) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t off = (int64_t)map * hw;
+    double acc[HM_MAXS][3];
+    float best[HM_MAXS + 1];
+    int bidx[HM_MAXS + 1];
+#pragma unroll
+    for (int s = 0; s <= HM_MAXS; ++s) { best[s] = -INFINITY; bidx[s] = 0x7fffffff; }
+#pragma unroll
+    for (int s = 0; s < HM_MAXS; ++s) acc[s][0] = acc[s][1] = acc[s][2] = 0.0;
+    // each thread walks its indices in increasing order, so '>' keeps the first maximum it sees
+#pragma unroll 2
+    for (int base = tid * 4; base < hw; base += 1024) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gt + off + base);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hm_take(g[i], base + i, best[HM_MAXS], bidx[HM_MAXS]);
+#pragma unroll
+        for (int s = 0; s < HM_MAXS; ++s) {
+            if (s < sets) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(a.pred[s] + off + base);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double d = fabs((double)p[i] - (double)g[i]);
+                    acc[s][0] += d;
+                    acc[s][1] += g[i] > 0.f ? d : 0.0;
+                    acc[s][2] += d * d;
+                    hm_take(p[i], base + i, best[s], bidx[s]);
+                }
+            }
+        }
+    }
+    __shared__ double s_acc[4][HM_MAXS * 3];
+    __shared__ float s_bv[4][HM_MAXS + 1];
+    __shared__ int s_bi[4][HM_MAXS + 1];
+#pragma unroll
+    for (int s = 0; s < HM_MAXS; ++s) {
+        if (s < sets) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double r = wave_sum_f64(acc[s][k]);
+                if (lane == 0) s_acc[wave][s * 3 + k] = r;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s <= HM_MAXS; ++s) {
+        if (s < sets || s == HM_MAXS) {
+            float bv = best[s];
+            int bi = bidx[s];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                hm_merge(ov, oi, bv, bi);
+            }
+            if (lane == 0) { s_bv[wave][s] = bv; s_bi[wave][s] = bi; }
+        }
+    }
+    __syncthreads();
+    if (tid < sets * 3)
+        partials[((int64_t)(tid / 3) * maps + map) * 3 + tid % 3] = ((s_acc[0][tid] + s_acc[1][tid]) + s_acc[2][tid]) + s_acc[3][tid];
+    if (tid >= 64 && tid - 64 <= HM_MAXS) {        // (a second wave: the two tails run side by side)
+        const int s = tid - 64;
+        if (s < sets || s == HM_MAXS) {
+            float bv = s_bv[0][s];
+            int bi = s_bi[0][s];
+            for (int w = 1; w < 4; ++w) hm_merge(s_bv[w][s], s_bi[w][s], bv, bi);
+            const int slot = s == HM_MAXS ? sets : s;          // the ground truth's row follows the sets'
+            argmax[(int64_t)slot * maps + map] = bi;
+            maxval[(int64_t)slot * maps + map] = bv;
+            if (s == HM_MAXS) valid[map] = bv >= thr ? 1 : 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void heatmap_finish_kernel(hm_args a, int sets, int groups, int B, int V, int J, int hw, int wid,
+                                                             const double* partials, const int32_t* argmax, const uint8_t* valid,
+                                                             float* l1, float* pos_l1, float* mse, float* mse_pts) {
+    const int s = blockIdx.x / groups, g = blockIdx.x - s * groups;
+    if (s >= sets) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int v0 = a.v0[g], v1 = a.v1[g];
+    const int64_t maps = (int64_t)B * V * J;
+    double sse = 0.0;
+    long long pts = 0;
+    for (int b = tid; b < B; b += 256) {
+        double sl1 = 0.0, spos = 0.0, ssq = 0.0;
+        for (int v = v0; v < v1; ++v)
+            for (int j = 0; j < J; ++j) {
+                const int64_t m = ((int64_t)b * V + v) * J + j;
+                const double* p = partials + ((int64_t)s * maps + m) * 3;
+                sl1 += p[0];
+                spos += p[1];
+                ssq += p[2];
+                if (valid[m]) {        // pts(pred) * valid - pts(gt) * valid: integer pixel coordinates
+                    const int pi = argmax[(int64_t)s * maps + m], gi = argmax[(int64_t)sets * maps + m];
+                    const int dx = pi % wid - gi % wid, dy = pi / wid - gi / wid;
+                    pts += (long long)(dx * dx + dy * dy);
+                }
+            }
+        l1[((int64_t)s * groups + g) * B + b] = (float)sl1;
+        pos_l1[((int64_t)s * groups + g) * B + b] = (float)spos;
+        sse += ssq;
+    }
+    __shared__ double s_sse[4];
+    __shared__ long long s_pts[4];
+    sse = wave_sum_f64(sse);
+    pts = wave_sum_i64(pts);
+    if (lane == 0) { s_sse[wave] = sse; s_pts[wave] = pts; }
+    __syncthreads();
+    if (tid == 0) {
+        const double n = (double)B * (double)(v1 - v0) * (double)J;
+        mse[s * groups + g] = (float)((((s_sse[0] + s_sse[1]) + s_sse[2]) + s_sse[3]) / (n * (double)hw));
+        mse_pts[s * groups + g] = (float)((double)(s_pts[0] + s_pts[1] + s_pts[2] + s_pts[3]) / (n * 2.0));
+    }
+}
+
+}  // namespace
+
+extern "C" int egr_heatmap_metrics_f32(const float* const* preds, int32_t sets, const float* gt, int32_t b, int32_t v, int32_t joints,
+                                       int32_t hgt, int32_t wid, const int32_t* view_groups, int32_t n_groups, float threshold,
+                                       double* partials, int32_t* argmax, float* maxval, uint8_t* valid, float* l1, float* pos_l1,
+                                       float* mse, float* mse_pts2d, void* stream) {
+    if (!preds || !gt || !view_groups || !partials || !argmax || !maxval || !valid || !l1 || !pos_l1 || !mse || !mse_pts2d) return EGR_ENULL;
+    if (sets < 1 || sets > HM_MAXS || n_groups < 1 || n_groups > HM_MAXG || b <= 0 || v <= 0 || joints <= 0 || joints > MAXJ ||
+        hgt <= 0 || wid <= 0)
+        return EGR_EINVAL;
+    const int64_t hw = (int64_t)hgt * wid, maps = (int64_t)b * v * joints;
+    if (hw % 4 != 0 || hw >= (1 << 24) || maps >= (1ll << 31) || ((uintptr_t)gt & 15)) return EGR_EINVAL;
+    hm_args a = {};
+    for (int s = 0; s < sets; ++s) {
+        if (!preds[s]) return EGR_ENULL;
+        if ((uintptr_t)preds[s] & 15) return EGR_EINVAL;
+        a.pred[s] = preds[s];
+    }
+    for (int g = 0; g < n_groups; ++g) {
+        a.v0[g] = view_groups[2 * g];
+        a.v1[g] = view_groups[2 * g + 1];
+        if (a.v0[g] < 0 || a.v1[g] > v || a.v0[g] >= a.v1[g]) return EGR_EINVAL;      // (an empty view group is refused)
+    }
+    hipLaunchKernelGGL(heatmap_partials_kernel, dim3((unsigned)maps), dim3(256), 0, (hipStream_t)stream, a, gt, sets, (int)maps, (int)hw,
+                       threshold, partials, argmax, maxval, valid);
+    hipLaunchKernelGGL(heatmap_finish_kernel, dim3((unsigned)(sets * n_groups)), dim3(256), 0, (hipStream_t)stream, a, sets, n_groups, b, v,
+                       joints, (int)hw, wid, partials, argmax, valid, l1, pos_l1, mse, mse_pts2d);
+    return egr_launch_status();
+}

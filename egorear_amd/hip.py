@@ -136,7 +136,7 @@ EXPORTS = [
     "egr_conv2d_nhwc_ex_f32", "egr_wh2_elems", "egr_pack_wh2_f32", "egr_absmax_f32", "egr_stem_conv7x7_x6_ex_f32", "egr_stem_wh2_bytes", "egr_pack_stem_wh2_f32", "egr_stem_conv7x7_h2_f32",
     "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2",
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
-    "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist",
+    "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
 ]
 
 
@@ -261,6 +261,8 @@ def _load() -> C.CDLL:
     lib.egr_conv2d_wgrad_ex_f32.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, C.c_size_t, i32, vp, vp, vp]
     lib.egr_gt_heatmap_f32.argtypes = [vp, i32, C.c_double, i32, i32, vp, vp, vp]
     lib.egr_pose_metrics_f32.argtypes = [vp, vp, i32, i32, f32, i32, vp, vp, vp]
+    lib.egr_heatmap_metrics_f32.argtypes = [C.POINTER(vp), i32, vp, i32, i32, i32, i32, i32, C.POINTER(i32), i32, f32,
+                                            vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.egr_pack_w6_f32.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.egr_pack_w6_many_f32.argtypes = [vp, i32, i64, vp]
     lib.egr_pack_wh2_many_f32.argtypes = [vp, i32, i64, i64, vp]

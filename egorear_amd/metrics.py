@@ -1,11 +1,20 @@
-"""Pose evaluation metrics on the device.
+"""Evaluation metrics on the device.
 
-Mirrors the reference's `evaluate_pose` (pl_wrappers/egoposeformer/pose_3d_mvf_ex.py:317-333) and the helpers it
+Pose: mirrors the reference's `evaluate_pose` (pl_wrappers/egoposeformer/pose_3d_mvf_ex.py:317-333) and the helpers it
 calls (utils/loss.py:9-48, models/utils/pose_metric.py:104-167) — same names, same units — but as ONE HIP kernel
-on the device tensors, instead of a device-to-host copy and a Python loop of numpy SVDs."""
+on the device tensors, instead of a device-to-host copy and a Python loop of numpy SVDs.
+
+Heat maps: `heatmap_metrics` / `evaluate_heatmap` mirror the `evaluate` of the two heat-map wrappers
+(pl_wrappers/egoposeformer/heatmap.py:220-254, heatmap_mvf_ex.py:263-316) and `evaluate_heatmap` of pose_3d_mvf_ex.py:335-361 —
+per-sample L1 error, L1 error where the ground truth is positive, MSE of the maps, MSE of the arg-max points under the ground
+truth's validity mask — as one pass over the maps (`egr_heatmap_metrics_f32`: every predicted set and view group in one call,
+fp64 sums in a fixed order), instead of a per-sample loop with boolean indexing and one device-to-host copy per sample.
+`egorear_amd.evaluate` builds the wrappers' validation / test steps on top of both."""
 from __future__ import annotations
 
+import ctypes as C
 from collections import OrderedDict
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -45,6 +54,72 @@ def evaluate_pose(pred_pose: torch.Tensor, gt_pose: torch.Tensor, prefix: str) -
     out[prefix + "_pck_3d"] = m[:, 2]
     out[prefix + "_auc_3d"] = m[:, 3]
     return out
+
+
+# --------------------------------------------------------------------------- heat-map metrics
+
+MAX_SETS, MAX_GROUPS = 4, 8      # EGR_HM_MAX_SETS / EGR_HM_MAX_GROUPS of include/egorear_hip.h
+
+
+def heatmap_metrics(pred_sets: Union[torch.Tensor, Sequence[torch.Tensor]], gt: torch.Tensor,
+                    view_groups: Optional[Sequence[Sequence[int]]] = None, threshold: float = 1.0) -> dict:
+    """One launch for S predicted sets (a tensor or a list of up to 4), each (B, V, J, H, W) fp32 contiguous on the device, one
+    ground truth of the same shape (float64 is cast) and G view groups [v0, v1) (None: one group of all views).  Raw device tensors:
+        l1, pos_l1 (S, G, B) fp32; mse, mse_pts2d (S, G) fp32                       - the reference's four quantities
+        argmax (S + 1, B, V, J) int32, maxval (S + 1, B, V, J) fp32: first maximum per map, the last row is the ground truth's;
+        valid (B, V, J) uint8 = [max(gt) >= threshold]; partials (S, B*V*J, 3) fp64 - the per-map sums behind the above.
+    Nothing synchronises: the call can be captured into a hipGraph."""
+    sets = [pred_sets] if isinstance(pred_sets, torch.Tensor) else list(pred_sets)
+    if not sets or not all(isinstance(t, torch.Tensor) for t in sets):
+        raise RuntimeError("egorear_amd.metrics.heatmap_metrics: a tensor or a non-empty list of tensors expected")
+    if not all(t.is_cuda for t in sets) or not gt.is_cuda:
+        raise RuntimeError("egorear_amd.metrics: device tensors expected (no CPU path)")
+    p0 = sets[0]
+    if p0.dim() != 5 or any(t.shape != p0.shape for t in sets) or gt.shape != p0.shape:
+        raise RuntimeError("egorear_amd.metrics.heatmap_metrics: every predicted set and gt must share one (B, V, J, H, W) shape")
+    B, V, J, H, W = (int(d) for d in p0.shape)
+    S = len(sets)
+    groups = [(0, V)] if view_groups is None else [(int(a), int(b)) for a, b in view_groups]
+    if S > MAX_SETS or not 1 <= len(groups) <= MAX_GROUPS or any(not 0 <= a < b <= V for a, b in groups):
+        raise RuntimeError(f"egorear_amd.metrics.heatmap_metrics: at most {MAX_SETS} sets and {MAX_GROUPS} non-empty view groups inside [0, {V})")
+    sets = [hip._cont(t.detach(), "a predicted heat-map set") for t in sets]
+    g = gt.detach()
+    if g.dtype == torch.float64:         # the dataset yields float64 ground truth
+        g = g.to(torch.float32)
+    g = hip._cont(g, "the ground-truth heat maps")
+    dev, G, maps = p0.device, len(groups), B * V * J
+    out = {"l1": torch.empty((S, G, B), device=dev, dtype=torch.float32), "pos_l1": torch.empty((S, G, B), device=dev, dtype=torch.float32),
+           "mse": torch.empty((S, G), device=dev, dtype=torch.float32), "mse_pts2d": torch.empty((S, G), device=dev, dtype=torch.float32),
+           "argmax": torch.empty((S + 1, B, V, J), device=dev, dtype=torch.int32), "maxval": torch.empty((S + 1, B, V, J), device=dev, dtype=torch.float32),
+           "valid": torch.empty((B, V, J), device=dev, dtype=torch.uint8), "partials": torch.empty((S, maps, 3), device=dev, dtype=torch.float64)}
+    ptrs = (C.c_void_p * S)(*[hip._p(t) for t in sets])
+    vg = (C.c_int32 * (2 * G))(*[x for ab in groups for x in ab])
+    hip._launch("egr_heatmap_metrics_f32", hip.lib.egr_heatmap_metrics_f32, ptrs, S, hip._p(g), B, V, J, H, W, vg, G, float(threshold),
+                hip._p(out["partials"], torch.float64), hip._p(out["argmax"], torch.int32), hip._p(out["maxval"]),
+                hip._p(out["valid"], torch.uint8), hip._p(out["l1"]), hip._p(out["pos_l1"]), hip._p(out["mse"]), hip._p(out["mse_pts2d"]),
+                hip._stream(), nbytes=4.0 * (S + 1) * maps * H * W)
+    return out
+
+
+def heatmap_dict(raw: dict, s: int, g: int, prefix: str, full: bool = True) -> "OrderedDict[str, torch.Tensor]":
+    """Set `s`, view group `g` of a `heatmap_metrics` result under the reference's key names, in its order."""
+    out = OrderedDict()
+    out[prefix + "_l1_error_heatmap"] = raw["l1"][s, g]
+    out[prefix + "_pos_l1_error_heatmap"] = raw["pos_l1"][s, g]
+    if full:
+        out[prefix + "_mse_heatmap"] = raw["mse"][s, g]
+        out[prefix + "_mse_pts2d"] = raw["mse_pts2d"][s, g]
+    return out
+
+
+def evaluate_heatmap(pred_heatmap: torch.Tensor, gt_heatmap: torch.Tensor, prefix: str, full: bool = True) -> "OrderedDict[str, torch.Tensor]":
+    """Same keys, order and shapes as the wrappers' `evaluate` (heatmap.py:220-254, heatmap_mvf_ex.py:263-316); full=False: the
+    two-key `evaluate_heatmap` of pose_3d_mvf_ex.py:335-361.  Values stay on the device: (B,), (B,), (), ().  View slices as the
+    wrappers pass them (`pred[:, 0:2]`) are accepted (copied dense); `heatmap_metrics(..., view_groups=...)` evaluates several
+    slices and sets in one launch without those copies."""
+    if not pred_heatmap.is_cuda or not gt_heatmap.is_cuda:
+        raise RuntimeError("egorear_amd.metrics: device tensors expected (no CPU path)")
+    return heatmap_dict(heatmap_metrics(pred_heatmap.detach().contiguous(), gt_heatmap.detach().contiguous()), 0, 0, prefix, full)
 
 
 # --------------------------------------------------------------------------- GT heat maps (SURVEY.md §8f rank 4)

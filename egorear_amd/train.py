@@ -1573,6 +1573,12 @@ class Trainer:
         from .dist import allreduce_mean_
         return allreduce_mean_(terms.clone(), self.opt.pg)
 
+    def evaluator(self):
+        """The validation / test step of this trainer's network (egorear_amd.evaluate): its own graphs and accumulators; the training
+        graph, the optimizer state and the BatchNorm buffers are not touched."""
+        from .evaluate import evaluator_for
+        return evaluator_for(self.net, self.opt.pg)
+
     def step(self, img, ctm, gt_pose, gt_heatmap):
         """Returns (loss terms (6,) float64 device tensor, outputs).  Parameters are updated in place."""
         from .dist import world_size

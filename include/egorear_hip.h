@@ -558,6 +558,27 @@ int egr_pose_metrics_f32(const float* pred, const float* gt, int32_t b, int32_t 
 int egr_gt_heatmap_f32(const double* joints, int32_t maps, double image_size, int32_t heatmap_size, int32_t tmp_size,
                        const float* gauss, float* out, void* stream);
 
+/* Heat-map validation metrics, replaces `evaluate` of pl_wrappers/egoposeformer/heatmap.py:220-254 and
+ * heatmap_mvf_ex.py:263-316 (with get_max_preds, utils/loss.py:122-142, threshold heatmap_mvf_ex.py:308-310) and
+ * `evaluate_heatmap` of pose_3d_mvf_ex.py:335-361 - a host loop with one device-to-host copy per sample there.
+ *   preds: HOST array of `sets` (1..EGR_HM_MAX_SETS) device pointers, each (b, v, joints, hgt, wid) fp32 dense, as is gt, which is
+ *   read once for all sets; view_groups: HOST array of n_groups (1..EGR_HM_MAX_GROUPS) pairs [v0, v1), 0 <= v0 < v1 <= v.
+ * Per map (work / by-products): partials (sets, b*v*joints, 3) fp64 = {sum |p-g|, the same where g > 0, sum (p-g)^2};
+ * argmax (sets + 1, b*v*joints) flat index of the first maximum and maxval (sets + 1, b*v*joints), row `sets` = the ground
+ * truth; valid (b*v*joints) = [max(gt) >= threshold].
+ * Per set and view group: l1, pos_l1 (sets, n_groups, b) per-sample sums over the group's views and all positions; mse
+ * (sets, n_groups) = mean of (p-g)^2; mse_pts2d (sets, n_groups) = mean over (b, group views, joints, 2) of
+ * (pts(p) * valid - pts(g) * valid)^2 with pts = (index % wid, index / wid).
+ * Sums accumulate in fp64 in a fixed order (no atomics): two calls on the same inputs give the same bits.  Two launches on
+ * `stream`, no synchronisation, no allocation.  EGR_EINVAL: hgt*wid not a multiple of 4, joints > 32, too many sets / groups,
+ * an empty or out-of-range view group, a pointer that is not 16-byte aligned. */
+#define EGR_HM_MAX_SETS 4
+#define EGR_HM_MAX_GROUPS 8
+int egr_heatmap_metrics_f32(const float* const* preds, int32_t sets, const float* gt, int32_t b, int32_t v, int32_t joints,
+                            int32_t hgt, int32_t wid, const int32_t* view_groups, int32_t n_groups, float threshold,
+                            double* partials, int32_t* argmax, float* maxval, uint8_t* valid, float* l1, float* pos_l1,
+                            float* mse, float* mse_pts2d, void* stream);
+
 /* The reference's only native call, in its own operand layout: mmcv==2.2.0 MultiScaleDeformableAttnFunction.apply
  * (models/utils/deform_attn.py:155-162; third-party, un-vendored, pin README.md:134).
  *   value (n, lin, heads, d) fp32, spatial_shapes i64 (levels, 2) = (H_l, W_l), level_start_index i64 (levels) — both
