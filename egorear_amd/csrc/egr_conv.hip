@@ -44,10 +44,6 @@ namespace {
 #define X6_OCC_BIG 2
 #endif
 
-// resident workgroup slots a persistent split-bf16 launch is sized for (2 per CU x 256 CUs); 0 = one workgroup per tile
-int g_persist = getenv("EGR_CONV_PERSIST") ? atoi(getenv("EGR_CONV_PERSIST")) : 512;
-int g_persist_ktiles = getenv("EGR_CONV_PERSIST_KTILES") ? atoi(getenv("EGR_CONV_PERSIST_KTILES")) : 4;   // K <= 128: persistent
-
 __device__ __attribute__((aligned(16))) float egr_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
 __device__ __forceinline__ void glds16(const float* g, float* l) {
@@ -1928,43 +1924,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_x6p_kernel(const ConvArgs a
     conv_igemm_body<BM, BN, WM, WN, true, true, false, false, NPL>(a);
 }
 
-template <int BM, int BN, int WM, int WN>
-int launch_cfg(ConvArgs& a, hipStream_t s) {
-    a.tilesM = (a.M + BM - 1) / BM;
-    a.tilesN = (a.Npad + BN - 1) / BN;
-    a.dTilesN = make_fastdiv(a.tilesN);
-    a.ntiles = a.tilesM * a.tilesN;
-    if (const int rc = bn_slabs(a)) return rc;
-    const int ny = a.cls_mode ? 4 : a.d.split_k;
-    int gx = a.ntiles;
-    bool persist = false;
-    const bool h2 = a.d.w_format == EGR_W_F16X2, x6 = h2 || a.d.w_format == EGR_W_BF16X3;
-    if (x6 && g_persist && BM * BN > 128 * 64 && a.ktiles <= g_persist_ktiles) {
-        // persistent launch: as many workgroups as stay resident (2 per CU, launch bounds), each walking `rounds` tiles; a
-        // multiple of 8 so that a workgroup's tiles keep its XCD (the tile order hands each XCD a contiguous run)
-        const int slots = (g_persist / (ny * a.d.groups)) & ~7;
-        if (slots >= 8 && a.ntiles > slots) {
-            const int rounds = (a.ntiles + slots - 1) / slots;
-            gx = ((a.ntiles + rounds - 1) / rounds + 7) & ~7;
-            persist = true;
-            a.cnt = nullptr;    // (short K: never split in practice) the persistent tile loop keeps the two-pass reduction
-        }
-    }
-    dim3 grid((unsigned)gx, (unsigned)ny, (unsigned)a.d.groups);
-    if (persist) {
-        if constexpr (BM * BN > 128 * 64) {
-            if (h2) hipLaunchKernelGGL((conv_igemm_x6p_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((conv_igemm_x6p_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), 0, s, a);
-        }
-    } else if (h2)
-        hipLaunchKernelGGL((conv_igemm_x6_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), 0, s, a);
-    else if (x6)
-        hipLaunchKernelGGL((conv_igemm_x6_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN>), grid, dim3(256), 0, s, a);
-    return egr_launch_status();
-}
-
 // fp32 weight matrix -> (hi, mid, lo) bf16 planes in MFMA-fragment order (layout: egorear_hip.h, egr_pack_w6_f32).
 // One workgroup per (32-column fragment, 32-deep chunk): thread (row = tid / 8, seg = tid % 8) reads 16 bytes of its weight row
 // (a row's 128 bytes are one coalesced segment) and writes 8 bytes per plane; the two threads of an 8-channel group and the 32
@@ -2090,22 +2049,46 @@ __global__ __launch_bounds__(256) void pack_wh2_many_kernel(const egr_wh2_job* _
     pack_wh2_block(j.w, j.descale, j.npad, j.k, cfp, reinterpret_cast<uint8_t*>(j.img), (int)(local % per_group), (int)(local / per_group));
 }
 
-enum { CFG_AUTO = -1, CFG_128x128 = 0, CFG_256x64 = 1, CFG_64x64 = 2, CFG_128x32 = 3, CFG_128x64 = 4, CFG_COUNT = 5 };
 const int kBM[CFG_COUNT] = {128, 256, 64, 128, 128};
 const int kBN[CFG_COUNT] = {128, 64, 64, 32, 64};
-int g_force_cfg = CFG_AUTO;
-int g_tap = getenv("EGR_CONV_TAP") ? atoi(getenv("EGR_CONV_TAP")) : 1;   // 0: the generic split kernel everywhere (egr_conv_set_tap)
-int g_tap2 = getenv("EGR_CONV_TAP2") ? atoi(getenv("EGR_CONV_TAP2")) : 1; // 0: stride-2 3x3 launches stay on the generic split kernel
-int g_last_conv_kernel = 0;   // diagnostic (tests): 0 fp32 MFMA, 1 split-bf16 generic, 2 / 3 split-bf16 tap-sharing (stride 1 / 2), 4 1x1 streaming
-int g_pw = getenv("EGR_CONV_PW") ? atoi(getenv("EGR_CONV_PW")) : 1;     // 0: short-K 1x1 split launches stay on the tiled kernels
-const int g_tap64_env = getenv("EGR_CONV_TAP64") ? atoi(getenv("EGR_CONV_TAP64")) : 1;
-int g_tap64 = g_tap64_env;    // 0: no 64-row tiles for the tap-sharing kernel's small launches
-int g_small = getenv("EGR_CONV_SMALL") ? atoi(getenv("EGR_CONV_SMALL")) : 1;        // 0: small fp32 1x1 launches stay on the tiled kernel
-int g_small_k = getenv("EGR_CONV_SMALL_K") ? atoi(getenv("EGR_CONV_SMALL_K")) : 1024;            // longest K (longer: split-K on the tiled kernel)
-int g_small_tiles = getenv("EGR_CONV_SMALL_TILES") ? atoi(getenv("EGR_CONV_SMALL_TILES")) : 256;  // most 32 x 32 tiles (all groups) for K > 64
-int g_small_rows = getenv("EGR_CONV_SMALL_ROWS") ? atoi(getenv("EGR_CONV_SMALL_ROWS")) : 8192;   // rows x groups up to which linear_small_kernel is used
-int g_pw_min_rows = getenv("EGR_CONV_PW_MIN_ROWS") ? atoi(getenv("EGR_CONV_PW_MIN_ROWS")) : 65536;   // rows x groups from which the streaming kernel is used
-int g_pw_blocks = getenv("EGR_CONV_PW_BLOCKS") ? atoi(getenv("EGR_CONV_PW_BLOCKS")) : 256;          // resident workgroups (one per CU)
+
+// The dispatch knobs: environment variable, default, meaning.  Read once, here; the setters below write the fields afterwards.
+ConvKnobs load_conv_knobs() {
+    auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    ConvKnobs k;
+    k.tap = env("EGR_CONV_TAP", 1);                    // 0: the generic split kernel everywhere (egr_conv_set_tap)
+    k.tap2 = env("EGR_CONV_TAP2", 1);                  // 0: stride-2 3x3 launches stay on the generic split kernel
+    k.tap64_env = env("EGR_CONV_TAP64", 1);            // 0: no 64-row tiles for the tap-sharing kernel's small launches
+    k.tap64 = k.tap64_env;                             //    (egr_conv_set_tap bit 1 clears it, bit 1 clear restores the environment's choice)
+    k.pw = env("EGR_CONV_PW", 1);                      // 0: short-K 1x1 split launches stay on the tiled kernels
+    k.pw_min_rows = env("EGR_CONV_PW_MIN_ROWS", 65536);    // rows x groups from which the streaming kernel is used
+    k.pw_blocks = env("EGR_CONV_PW_BLOCKS", 256);      // its resident workgroups (one per CU)
+    k.small = env("EGR_CONV_SMALL", 1);                // 0: small fp32 1x1 launches stay on the tiled kernel
+    k.small_k = env("EGR_CONV_SMALL_K", 1024);         // longest K (longer: split-K on the tiled kernel)
+    k.small_tiles = env("EGR_CONV_SMALL_TILES", 256);  // most 32 x 32 tiles (all groups) for K > 64
+    k.small_rows = env("EGR_CONV_SMALL_ROWS", 8192);   // rows x groups up to which linear_small_kernel is used
+    // resident workgroup slots a persistent split-bf16 launch is sized for (2 per CU x 256 CUs); 0 = one workgroup per tile
+    k.persist = env("EGR_CONV_PERSIST", 512);
+    k.persist_ktiles = env("EGR_CONV_PERSIST_KTILES", 4);  // K <= 128: persistent
+    k.force_cfg = CFG_AUTO;                            // egr_conv_force_config only
+    // 1: the last-arriving K slice of a tile reduces it (no second launch).  Correct and deterministic, but measured SLOWER than the
+    // second pass (batch 1: 2.36 against 1.76 ms over 25 split launches; batch 64: 15.35 against 15.26 ms): the slabs must then be
+    // written and read with agent-scope (`sc1`) accesses that go to memory, and one workgroup sums a tile that the second pass
+    // spreads over the chip.  Opt-in (egr_conv_set_splitk_fused / EGR_SPLITK_FUSED=1).
+    k.splitk_fused = env("EGR_SPLITK_FUSED", 0);
+    k.splitk_mid_kt = env("EGR_SPLITK_MID_KT", 16);    // fp32 launches of 128 .. 511 workgroups split K from this many chunks (0: from 64 only)
+    k.splitk_target = env("EGR_SPLITK_TARGET", 1024);  // workgroups an automatic split-K aims at (4 per CU)
+    k.tapx = env("EGR_CONV_TAPX", 1);                  // 0: the 3x3 launches stay on conv_igemm_tap[2]_kernel
+    k.tapx_min_tiles = env("EGR_CONV_TAPX_MIN_TILES", 256);    // tiles (all groups) from which the role-split kernel is used
+    k.tapx_blocks = env("EGR_CONV_TAPX_BLOCKS", 256);  // resident workgroups (one per CU)
+    k.tapx_pw = env("EGR_CONV_TAPX_PW", 1);            // 0: 1x1 launches with >= 256 input channels stay on the tiled kernel
+    k.tapx_tpw = env("EGR_CONV_TAPX_TPW", 0);          // > 0: tiles per workgroup of a non-persistent launch (experiment)
+    k.tapx_train = env("EGR_CONV_TAPX_TRAIN", 1);      // 0: statistics-epilogue / masked launches stay on conv_igemm_tap_kernel
+    k.tapx_fn = env("EGR_CONV_TAPX_FN", 0);            // wave tile: 0 by shape, 1: 128 x 32, 2: 128 x 64 wherever it exists
+    return k;
+}
+ConvKnobs g_knobs = load_conv_knobs();
+int g_last_conv_kernel = 0;   // diagnostic (tests): the route (egr_conv_route) of the last plan that was launched
 unsigned long long* g_dbg = nullptr;
 // split-K arrival counters: one region per WORKSPACE (the slab buffer the K slices are written to).  Two launches that share a
 // workspace can never overlap (they would race on the slabs themselves), two launches with different workspaces may - the graphs of
@@ -2115,11 +2098,6 @@ unsigned long long* g_dbg = nullptr;
 // 65th workspace of a process gets none and its launches take the second pass.
 constexpr int SPLITK_REGION = 2048, SPLITK_REGIONS = 64;
 __device__ int g_splitk_cnt[SPLITK_REGION * SPLITK_REGIONS];
-// 1: the last-arriving K slice of a tile reduces it (no second launch).  Correct and deterministic, but measured SLOWER than the
-// second pass (batch 1: 2.36 against 1.76 ms over 25 split launches; batch 64: 15.35 against 15.26 ms): the slabs must then be
-// written and read with agent-scope (`sc1`) accesses that go to memory, and one workgroup sums a tile that the second pass
-// spreads over the chip.  Opt-in (egr_conv_set_splitk_fused / EGR_SPLITK_FUSED=1).
-int g_splitk_fused = getenv("EGR_SPLITK_FUSED") ? atoi(getenv("EGR_SPLITK_FUSED")) : 0;
 const void* g_splitk_keys[SPLITK_REGIONS];
 int g_splitk_nkeys = 0;
 std::mutex g_splitk_mu;
@@ -2187,95 +2165,135 @@ extern "C" int egr_pack_wh2_many_f32(const egr_wh2_job* jobs, int32_t count, int
     return egr_launch_status();
 }
 
+// ---- knob setters (diagnostic / test; process-wide - include/egorear_hip.h says what each does)
+extern "C" int egr_conv_set_persist(int slots, int max_ktiles) {       // negative: unchanged
+    if (slots >= 0) g_knobs.persist = slots;
+    if (max_ktiles >= 0) g_knobs.persist_ktiles = max_ktiles;
+    return 0;
+}
+extern "C" int egr_conv_set_splitk_fused(int on) { g_knobs.splitk_fused = on; return 0; }
+extern "C" int egr_conv_set_tap(int on) { g_knobs.tap = on & 1; g_knobs.tap64 = (on & 2) ? 0 : g_knobs.tap64_env; return 0; }     // (bit 1: no 64-row tiles; clear: what EGR_CONV_TAP64 chose)
+extern "C" int egr_conv_set_tapx(int32_t on, int32_t min_tiles, int32_t blocks) {
+    if (on >= 0) { g_knobs.tapx = on != 0; g_knobs.tapx_fn = on >= 2 ? on - 1 : 0; }      // on = 2 / 3: the 128 x 32 / 128 x 64 wave tile wherever it exists (tests)
+    if (min_tiles >= 0) g_knobs.tapx_min_tiles = min_tiles;
+    if (blocks > 0) g_knobs.tapx_blocks = blocks;
+    return 0;
+}
+extern "C" int egr_conv_force_config(int cfg) {
+    if (cfg < CFG_AUTO || cfg >= CFG_COUNT) return EGR_EINVAL;
+    g_knobs.force_cfg = cfg;
+    return 0;
+}
 extern "C" int egr_conv_debug_stamps(unsigned long long* buf) {  // diagnostic: 8 x u64 per workgroup, NULL = off
     g_dbg = buf;
     return 0;
 }
-
-// diagnostic / test knob: resident workgroup slots a persistent split-bf16 launch is sized for (0 = never persistent) and the
-// largest K (in 32-deep chunks) that takes the persistent kernel.  Negative values leave a setting unchanged.  Defaults: 512, 4.
-extern "C" int egr_conv_set_persist(int slots, int max_ktiles) {
-    if (slots >= 0) g_persist = slots;
-    if (max_ktiles >= 0) g_persist_ktiles = max_ktiles;
-    return 0;
-}
-
 extern "C" int egr_conv_last_kernel(void) { return g_last_conv_kernel; }
-extern "C" int egr_conv_set_splitk_fused(int on) { g_splitk_fused = on; return 0; }
-extern "C" int egr_conv_set_tap(int on) { g_tap = on & 1; g_tap64 = (on & 2) ? 0 : g_tap64_env; return 0; }     // (bit 1: no 64-row tiles; clear: what EGR_CONV_TAP64 chose)
-extern "C" int egr_conv_set_tapx(int32_t on, int32_t min_tiles, int32_t blocks) { return tapx_set(on, min_tiles, blocks); }
 
-extern "C" int egr_conv_force_config(int cfg) {
-    if (cfg < CFG_AUTO || cfg >= CFG_COUNT) return EGR_EINVAL;
-    g_force_cfg = cfg;
-    return 0;
+// ================================================================================================================================
+// A conv call is four steps: conv_check (refuse) -> conv_geometry (derive) -> conv_plan (decide, pure host) -> conv_launch (apply and
+// launch).  egr_conv_plan stops after the third.
+namespace {
+
+struct ConvOperands {
+    const float *x, *w, *scale, *shift, *res, *rowscale;
+    const uint8_t* rowmask;
+    const float* mask;
+    float *y, *workspace;
+    size_t workspace_floats;
+    const egr_conv_aux* aux;
+};
+
+// furthest float image n - 1 starts at
+int64_t map_span(const egr_nmap& m, int n) {
+    int o = (n - 1) / m.n_inner, i = (n - 1 < m.n_inner ? n - 1 : m.n_inner - 1);
+    return (int64_t)i * m.stride_inner + (int64_t)o * m.stride_outer;
+}
+int64_t y_span(const egr_conv_desc& d) {
+    return map_span(d.ymap, d.n) + (d.out_nchw ? (int64_t)d.cout * d.ho * d.wo : (int64_t)d.ho * d.wo * d.ldy);
+}
+int64_t r_span(const egr_conv_desc& d) { return map_span(d.rmap, d.n) + (int64_t)d.ho * d.wo * d.ldr; }   // (upper bound for the half-size mode too)
+
+// 16-byte epilogue accesses need every (row, channel-quad) address aligned
+bool epilogue_vec_ok(const egr_conv_desc& d, const ConvOperands& o) {
+    bool ok = !d.out_nchw && (d.ldy % 4 == 0) && (((uintptr_t)o.y & 15) == 0) && ((d.ymap.stride_inner | d.ymap.stride_outer) % 4 == 0) &&
+              (!o.scale || ((uintptr_t)o.scale & 15) == 0) && (!o.shift || ((uintptr_t)o.shift & 15) == 0);
+    if (d.res_mode)
+        ok = ok && (d.ldr % 4 == 0) && (((uintptr_t)o.res & 15) == 0) && ((d.rmap.stride_inner | d.rmap.stride_outer) % 4 == 0);
+    return ok;
 }
 
-static int conv_run(const egr_conv_desc* dd, const float* x, const float* w, const float* scale, const float* shift, const float* res,
-                    const float* rowscale, const uint8_t* rowmask, const float* mask, float* y, float* workspace,
-                    size_t workspace_floats, const egr_conv_aux* aux, void* stream) {
-    if (!dd || !x || !w || !y) return EGR_ENULL;
-    ConvArgs a;
-    a.d = *dd;
-    egr_conv_desc& d = a.d;
+// ---- 1. check: 0 or the EGR_E* code of the first rule the call breaks
+int conv_check(const egr_conv_desc& d, const ConvOperands& o) {
+    const egr_conv_aux* aux = o.aux;
+    if (!o.x || !o.w || !o.y) return EGR_ENULL;
     if (d.cin <= 0 || d.cin % BK != 0 || d.cout <= 0 || d.kh <= 0 || d.kw <= 0 || d.stride <= 0) return EGR_EINVAL;
     if (d.n <= 0 || d.ho <= 0 || d.wo <= 0 || d.kh * d.kw > 32) return EGR_EINVAL;
-    if (d.ldx % 4 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return EGR_EINVAL;  // 16-byte A/B loads
-    if (d.res_mode != EGR_RES_NONE && !res) return EGR_ENULL;
+    if (d.ldx % 4 != 0 || ((uintptr_t)o.x & 15) || ((uintptr_t)o.w & 15)) return EGR_EINVAL;  // 16-byte A/B loads
+    if (d.res_mode != EGR_RES_NONE && !o.res) return EGR_ENULL;
     if (d.xmap.n_inner <= 0 || d.ymap.n_inner <= 0 || (d.res_mode && d.rmap.n_inner <= 0)) return EGR_EINVAL;
     if ((d.xmap.stride_inner | d.xmap.stride_outer) % 4 != 0) return EGR_EINVAL;
-    if (d.groups <= 0) d.groups = 1;
     if (d.groups > 1 && ((d.gx | d.gw | d.gp | d.gy | d.gr) % 4 != 0)) return EGR_EINVAL;  // keep 16-byte alignment per group
     if (d.groups > 65535) return EGR_EINVAL;
     if (d.w_format != EGR_W_F32 && d.w_format != EGR_W_BF16X3 && d.w_format != EGR_W_F16X2) return EGR_EINVAL;
     const bool h2 = d.w_format == EGR_W_F16X2, x6 = h2 || d.w_format == EGR_W_BF16X3;   // split kernels (bf16 x 3 / fp16 x 2)
     if (x6 && d.groups > 1 && d.gw % 8 != 0) return EGR_EINVAL;
-    // the fp16 scheme needs the weights' descale and the activations' abs-max record; forward launches only for now
+    // the fp16 scheme needs the weights' descale and the activations' abs-max record
     if (h2 && (!aux || !aux->w_descale || !aux->amax_in)) return EGR_ENULL;
     if (h2 && (((uintptr_t)aux->amax_in) & 3)) return EGR_EINVAL;
     if (aux && aux->amax_out && d.out_nchw) return EGR_EINVAL;   // the channel-major epilogue does not record max |y|
-    int64_t M64 = (int64_t)d.n * d.ho * d.wo;
-    if (M64 >= (1LL << 31)) return EGR_EINVAL;
+    if ((int64_t)d.n * d.ho * d.wo >= (1LL << 31)) return EGR_EINVAL;
     // 32-bit offsets inside the kernel: bound the furthest element each operand can touch
-    auto span = [](const egr_nmap& m, int n) {
-        int o = (n - 1) / m.n_inner, i = (n - 1 < m.n_inner ? n - 1 : m.n_inner - 1);
-        return (int64_t)i * m.stride_inner + (int64_t)o * m.stride_outer;
-    };
-    if (span(d.xmap, d.n) + (int64_t)d.h * d.w * d.ldx >= (1LL << 31)) return EGR_EINVAL;
-    int64_t ypix = d.out_nchw ? (int64_t)d.cout * d.ho * d.wo : (int64_t)d.ho * d.wo * d.ldy;
-    if (span(d.ymap, d.n) + ypix >= (1LL << 31)) return EGR_EINVAL;
-    if (d.res_mode && span(d.rmap, d.n) + (int64_t)d.ho * d.wo * d.ldr >= (1LL << 31)) return EGR_EINVAL;   // (upper bound for the half-size mode too)
+    const int64_t xspan = map_span(d.xmap, d.n) + (int64_t)d.h * d.w * d.ldx;
+    if (xspan >= (1LL << 31)) return EGR_EINVAL;
+    if (y_span(d) >= (1LL << 31)) return EGR_EINVAL;
+    if (d.res_mode && r_span(d) >= (1LL << 31)) return EGR_EINVAL;
     // split-bf16 launches address the activations through a 2-GiB buffer window (byte offsets, shifted by the halo bias)
-    if (x6 &&
-        (span(d.xmap, d.n) + (int64_t)d.h * d.w * d.ldx + 2 * (int64_t)(d.kh * d.w + d.kw + 1) * d.ldx) * 4 + 64 >= (1LL << 31))
-        return EGR_EINVAL;
-
-    a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.rowscale = rowscale; a.rowmask = rowmask;
-    a.y = y; a.ws = workspace;
-    a.mask = mask;
-    a.wds = aux ? aux->w_descale : nullptr;
-    a.amax_in = aux ? aux->amax_in : nullptr;
-    a.amax_out = aux ? aux->amax_out : nullptr;
+    if (x6 && (xspan + 2 * (int64_t)(d.kh * d.w + d.kw + 1) * d.ldx) * 4 + 64 >= (1LL << 31)) return EGR_EINVAL;
     // train-mode BatchNorm statistics in the epilogue (egr_conv_aux.bn_partials): the plain 16-byte epilogue of a raw conv output only
     const bool bnst = aux && aux->bn_partials;
-    a.bn_part = bnst ? aux->bn_partials : nullptr;
-    a.bn_tiles_host = bnst ? aux->bn_tiles_out : nullptr;
-    a.bn_cap = bnst ? (size_t)aux->bn_capacity : 0;
     if (bnst) {
         if (!aux->bn_tiles_out) return EGR_ENULL;
-        if (mask || d.transposed || d.out_nchw || d.act != EGR_ACT_NONE || d.res_mode != EGR_RES_NONE || rowscale || rowmask ||
+        if (o.mask || d.transposed || d.out_nchw || d.act != EGR_ACT_NONE || d.res_mode != EGR_RES_NONE || o.rowscale || o.rowmask ||
             d.cout % 64 != 0 || ((uintptr_t)aux->bn_partials & 15))
             return EGR_EINVAL;
-        d.split_k = 1;        // (the statistics are taken where the tile is stored, not in a split-K reduction)
     }
+    const bool vec_ok = epilogue_vec_ok(d, o);
+    if (d.res_mode == EGR_RES_UP2_BEFORE_ACT &&   // residual upsampled on the fly: 16-byte path, even output size, ReLU / none
+        (!vec_ok || d.cout % 4 != 0 || o.rowscale || o.rowmask || o.mask || d.out_nchw || d.transposed || (d.ho & 1) || (d.wo & 1) ||
+         d.act == EGR_ACT_GELU))
+        return EGR_EINVAL;
+    if (bnst && !vec_ok) return EGR_EINVAL;
+    if (o.mask &&   // masked data gradient: plain 16-byte epilogue only
+        (!vec_ok || d.cout % 4 != 0 || o.scale || o.shift || o.rowscale || o.rowmask || d.act != EGR_ACT_NONE || d.out_nchw ||
+         d.res_mode == EGR_RES_AFTER_ACT || ((uintptr_t)o.mask & 15)))
+        return EGR_EINVAL;
+    return 0;
+}
+
+// ---- 2. geometry: every field of ConvArgs that does not depend on the kernel chosen (the plan's share - tiles, split - is conv_launch's)
+void conv_geometry(ConvArgs& a, const egr_conv_desc& dd, const ConvOperands& o, unsigned long long* dbg) {
+    a.d = dd;
+    egr_conv_desc& d = a.d;
+    if (d.groups <= 0) d.groups = 1;
+    a.x = o.x; a.w = o.w; a.scale = o.scale; a.shift = o.shift; a.res = o.res; a.rowscale = o.rowscale; a.rowmask = o.rowmask;
+    a.y = o.y; a.ws = o.workspace;
+    a.mask = o.mask;
+    a.wds = o.aux ? o.aux->w_descale : nullptr;
+    a.amax_in = o.aux ? o.aux->amax_in : nullptr;
+    a.amax_out = o.aux ? o.aux->amax_out : nullptr;
+    const bool bnst = o.aux && o.aux->bn_partials;
+    a.bn_part = bnst ? o.aux->bn_partials : nullptr;
+    a.bn_tiles_host = bnst ? o.aux->bn_tiles_out : nullptr;
+    a.bn_cap = bnst ? (size_t)o.aux->bn_capacity : 0;
     a.cnt = nullptr;
-    a.dbg = g_dbg;
-    a.M = (int)M64;
+    a.dbg = dbg;
+    a.M = d.n * d.ho * d.wo;
     a.Npad = (d.cout + 31) / 32 * 32;
     a.K = d.kh * d.kw * d.cin;
     auto log2_exact = [](int v) { int l = 0; while ((1 << l) < v) ++l; return ((1 << l) == v) ? l : -1; };
     // stride-2 data gradient with even output size: four parity classes, each enumerating a (ho/2, wo/2) grid
-    a.cls_mode = (d.transposed && d.stride == 2 && (d.ho % 2 == 0) && (d.wo % 2 == 0) && !d.out_nchw && !rowscale && !rowmask &&
+    a.cls_mode = (d.transposed && d.stride == 2 && (d.ho % 2 == 0) && (d.wo % 2 == 0) && !d.out_nchw && !o.rowscale && !o.rowmask &&
                   d.split_k <= 1) ? 1 : 0;
     const int eho = a.cls_mode ? d.ho / 2 : d.ho, ewo = a.cls_mode ? d.wo / 2 : d.wo;
     if (a.cls_mode) a.M = d.n * eho * ewo;
@@ -2292,158 +2310,106 @@ static int conv_run(const egr_conv_desc* dd, const float* x, const float* w, con
     a.cblocks = d.cin / BK;
     a.taps = d.kh * d.kw;
     a.ktiles = a.taps * a.cblocks;
-    // 16-byte epilogue accesses need every (row, channel-quad) address aligned
-    a.vec_ok = !d.out_nchw && (d.ldy % 4 == 0) && (((uintptr_t)y & 15) == 0) &&
-               ((d.ymap.stride_inner | d.ymap.stride_outer) % 4 == 0) &&
-               (!scale || ((uintptr_t)scale & 15) == 0) && (!shift || ((uintptr_t)shift & 15) == 0);
-    if (d.res_mode)
-        a.vec_ok = a.vec_ok && (d.ldr % 4 == 0) && (((uintptr_t)res & 15) == 0) &&
-                   ((d.rmap.stride_inner | d.rmap.stride_outer) % 4 == 0);
-    if (d.res_mode == EGR_RES_UP2_BEFORE_ACT) {  // residual upsampled on the fly: 16-byte path, even output size, ReLU / none
-        if (!a.vec_ok || d.cout % 4 != 0 || rowscale || rowmask || mask || d.out_nchw || d.transposed || (d.ho & 1) || (d.wo & 1) ||
-            d.act == EGR_ACT_GELU)
-            return EGR_EINVAL;
-        d.split_k = 1;
-    }
-    if (bnst && !a.vec_ok) return EGR_EINVAL;
-    if (mask) {  // masked data gradient: plain 16-byte epilogue only
-        if (!a.vec_ok || d.cout % 4 != 0 || scale || shift || rowscale || rowmask || d.act != EGR_ACT_NONE || d.out_nchw ||
-            d.res_mode == EGR_RES_AFTER_ACT || ((uintptr_t)mask & 15))
-            return EGR_EINVAL;
-        d.split_k = 1;   // the mask is applied in the tile epilogue, not in the split-K reduction
-    }
+    a.vec_ok = epilogue_vec_ok(d, o);
+    // epilogues that work on whole sums: the statistics are taken, the up-sampled residual added and the mask applied where the tile is
+    // stored, not in a split-K reduction (after cls_mode, which looks at the split the caller asked for)
+    if (bnst || d.res_mode == EGR_RES_UP2_BEFORE_ACT || o.mask) d.split_k = 1;
+}
 
-    // ---- small fp32 1x1 / stride 1 launches: one 32 x 32 tile per workgroup, K split over its four waves (linear_small_kernel)
-    if (g_small && g_force_cfg == CFG_AUTO && !x6 && d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad == 0 && d.h == d.ho && d.w == d.wo &&
-        !d.out_nchw && !mask && !a.cls_mode && !bnst && d.res_mode != EGR_RES_UP2_BEFORE_ACT && a.K % 32 == 0 && a.K <= g_small_k && d.split_k <= 1 &&
-        (int64_t)a.M * d.groups <= g_small_rows) {
-        a.tilesM = (a.M + 31) / 32;
-        a.tilesN = a.Npad / 32;
-        const int64_t tiles = (int64_t)a.tilesM * a.tilesN;
-        // (measured inside a hipGraph, per launch: 64 tiles K 128 4.1 us against 6.5 tiled, 256 tiles K 512 12.2 against 16.2, 1024 tiles
-        // K 64 6.0 against 10.6 - but 1024 tiles K 128 25 against 12, and M 32 x K 32768 0.34 ms against 0.11 with split-K)
-        if (tiles * d.groups <= g_small_tiles || a.K <= 64) {
-            hipLaunchKernelGGL(linear_small_kernel, dim3((unsigned)tiles, 1, (unsigned)d.groups), dim3(256), 0, (hipStream_t)stream, a);
-            g_last_conv_kernel = 5;
-            return egr_launch_status();
-        }
-    }
+// ---- 3. plan: the routes in the order they are tried.  Each fills `out` completely or leaves it untouched; none touches the device.
 
-    // ---- the fp16 scheme's 3x3 (and wide 1x1) launches with enough tiles - forward, and the training step's statistics-epilogue and
-    // stride-1 data-gradient (plain / masked) ones: role-split persistent workgroups (egr_conv_tapx.hip)
-    if (g_tap && g_force_cfg == CFG_AUTO && h2 && ((d.kh == 3 && d.kw == 3) || (d.kh == 1 && d.kw == 1 && d.cin >= 256))) {
-        const int rc = tapx_try(a, span(d.ymap, d.n) + ypix, d.res_mode ? span(d.rmap, d.n) + (int64_t)d.ho * d.wo * d.ldr : 0, (hipStream_t)stream);
-        if (rc != TAPX_NO) {
-            g_last_conv_kernel = 6;
-            return rc;
-        }
-    }
-    // ---- 3x3 / stride 1 / pad 1 split launches whose tiles are whole image rows: the tap-sharing kernel
-    if (g_tap && g_force_cfg == CFG_AUTO && x6 && d.kh == 3 && d.kw == 3 && d.stride == 1 && d.pad == 1 &&
-        !a.cls_mode && d.split_k <= 1 && (d.wo == 8 || d.wo == 16 || d.wo == 32 || d.wo == 64) && d.ho == d.h && d.wo == d.w &&
-        a.Npad % 64 == 0 && a.M >= 2048) {
-        // 256 x 64 tiles for 64 / 192 output channels (as many MFMAs per tap as 128 x 128), 128 x 128 when that fills the chip, else 128 x 64
-        const int P = d.ho * d.wo;
-        auto fits_tile = [&](int bm) {
-            if (a.M % bm != 0 || !((P % bm == 0) || (bm % P == 0))) return false;
-            const int hp = P >= bm ? (bm / d.wo + 2) * (d.wo + 2) : (bm / P) * (d.ho + 2) * (d.wo + 2);
-            return hp <= tap_hpmax(bm);
-        };
-        int bm = 0, bn = 0;
-        if (a.Npad % 128 == 0 && fits_tile(128) && (int64_t)(a.M / 128) * (a.Npad / 128) * d.groups >= 256) { bm = 128; bn = 128; }
-        else if (fits_tile(256) && (int64_t)(a.M / 256) * (a.Npad / 64) * d.groups >= 256) { bm = 256; bn = 64; }
-        else if (fits_tile(128)) { bm = 128; bn = 64; }
-        // few rows (batch 1: layer1 has 128 tiles of 128 x 64, layer2 64): 64-row tiles put twice the workgroups on the chip
-        if (g_tap64 && h2 && bm == 128 && bn == 64 && !bnst && fits_tile(64) && (int64_t)(a.M / 128) * (a.Npad / 64) * d.groups < 256) bm = 64;
-        if (bm) {
-            d.split_k = 1;
-            a.ktiles_per_split = a.ktiles;
-            a.tilesM = a.M / bm;
-            a.tilesN = a.Npad / bn;
-            a.dTilesN = make_fastdiv(a.tilesN);
-            a.ntiles = a.tilesM * a.tilesN;
-            if (const int rcb = bn_slabs(a)) return rcb;
-            dim3 grid((unsigned)a.ntiles, 1, (unsigned)d.groups);
-            if (h2) {
-                if (bm == 64) hipLaunchKernelGGL((conv_igemm_tap_kernel<64, 64, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-                else if (bm == 256) hipLaunchKernelGGL((conv_igemm_tap_kernel<256, 64, 4, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-                else if (bn == 128) hipLaunchKernelGGL((conv_igemm_tap_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-                else hipLaunchKernelGGL((conv_igemm_tap_kernel<128, 64, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            } else if (bm == 256) hipLaunchKernelGGL((conv_igemm_tap_kernel<256, 64, 4, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            else if (bn == 128) hipLaunchKernelGGL((conv_igemm_tap_kernel<128, 128, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL((conv_igemm_tap_kernel<128, 64, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            g_last_conv_kernel = 2;
-            return egr_launch_status();
-        }
-    }
-    // ---- 3x3 / stride 2 / pad 1 split launches on even images: taps shared by parity class
-    if (g_tap && g_tap2 && g_force_cfg == CFG_AUTO && x6 && d.kh == 3 && d.kw == 3 && d.stride == 2 && d.pad == 1 &&
-        !d.transposed && !a.cls_mode && d.split_k <= 1 && !mask && (d.wo == 8 || d.wo == 16 || d.wo == 32) &&
-        d.h == 2 * d.ho && d.w == 2 * d.wo && a.Npad % 64 == 0 && a.M >= 2048 && a.M % 128 == 0) {
-        const int P = d.ho * d.wo;
-        const int hp = P >= 128 ? (128 / d.wo + 1) * (d.wo + 1) : (128 / P) * (d.ho + 1) * (d.wo + 1);
-        if (((P % 128 == 0) || (128 % P == 0)) && hp <= 192) {
-            const int bn = (a.Npad % 128 == 0 && (int64_t)(a.M / 128) * (a.Npad / 128) * d.groups >= 256) ? 128 : 64;
-            d.split_k = 1;
-            a.ktiles_per_split = a.ktiles;
-            a.tilesM = a.M / 128;
-            a.tilesN = a.Npad / bn;
-            a.dTilesN = make_fastdiv(a.tilesN);
-            a.ntiles = a.tilesM * a.tilesN;
-            if (const int rcb = bn_slabs(a)) return rcb;
-            dim3 grid((unsigned)a.ntiles, 1, (unsigned)d.groups);
-            if (h2) {
-                if (bn == 128) hipLaunchKernelGGL((conv_igemm_tap2_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-                else hipLaunchKernelGGL((conv_igemm_tap2_kernel<128, 64, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            } else if (bn == 128) hipLaunchKernelGGL((conv_igemm_tap2_kernel<128, 128, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL((conv_igemm_tap2_kernel<128, 64, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-            g_last_conv_kernel = 3;
-            return egr_launch_status();
-        }
-    }
-    // ---- 1x1 / stride 1 split launches with cin = 64 / 128 over many pixels: weights stationary in LDS, activations streamed
-    if (g_tap && g_pw && !bnst && g_force_cfg == CFG_AUTO && x6 && d.kh == 1 && d.kw == 1 && d.pad == 0 &&
-        (d.stride == 1 || (d.stride == 2 && !d.transposed && d.ho == (d.h - 1) / 2 + 1 && d.wo == (d.w - 1) / 2 + 1)) &&
-        !a.cls_mode && d.split_k <= 1 && !d.out_nchw && !rowscale && !rowmask && a.vec_ok && d.cout % 4 == 0 &&
-        d.act != EGR_ACT_GELU && (d.cin == 64 || d.cin == 128) && a.Npad % 64 == 0 && (d.stride == 2 || (d.h == d.ho && d.w == d.wo)) &&
-        (int64_t)a.M * d.groups >= g_pw_min_rows && (span(d.ymap, d.n) + ypix) * 4 < (1LL << 31) &&
-        (!d.res_mode || (span(d.rmap, d.n) + (int64_t)d.ho * d.wo * d.ldr) * 4 < (1LL << 31))) {
-        const int ncf = (a.Npad % 128 == 0) ? 4 : 2;
-        const int tiles_n = a.Npad / (ncf * 32);
-        int nblk = g_pw_blocks / (tiles_n * d.groups);
-        if (nblk < 1) nblk = 1;
-        const int t32 = (a.M + 31) / 32;
-        if (nblk * 8 > t32) nblk = (t32 + 7) / 8;
-        dim3 grid((unsigned)nblk, (unsigned)tiles_n, (unsigned)d.groups);
-        const int resk = d.res_mode == EGR_RES_NONE ? 0 : (d.res_mode == EGR_RES_UP2_BEFORE_ACT ? 2 : 1);
-        auto launch = [&](auto ks_tag, auto ncf_tag) {
-            constexpr int KS = decltype(ks_tag)::value, NCF = decltype(ncf_tag)::value;
-            if (h2) {
-                if (resk == 0) hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 0, 2>), grid, dim3(512), 0, (hipStream_t)stream, a);
-                else if (resk == 1) hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 1, 2>), grid, dim3(512), 0, (hipStream_t)stream, a);
-                else hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 2, 2>), grid, dim3(512), 0, (hipStream_t)stream, a);
-            } else if (resk == 0) hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 0>), grid, dim3(512), 0, (hipStream_t)stream, a);
-            else if (resk == 1) hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 1>), grid, dim3(512), 0, (hipStream_t)stream, a);
-            else hipLaunchKernelGGL((conv_pw_x6_kernel<KS, NCF, 2>), grid, dim3(512), 0, (hipStream_t)stream, a);
-        };
-        using C2 = std::integral_constant<int, 2>;
-        using C4 = std::integral_constant<int, 4>;
-        using C8 = std::integral_constant<int, 8>;
-        if (d.cin == 128 && ncf == 4) launch(C8{}, C4{});
-        else if (d.cin == 128) launch(C8{}, C2{});
-        else if (ncf == 4) launch(C4{}, C4{});
-        else launch(C4{}, C2{});
-        g_last_conv_kernel = 4;
-        return egr_launch_status();
-    }
-    g_last_conv_kernel = x6 ? 1 : 0;
+// small fp32 1x1 / stride 1 launches: one 32 x 32 tile per workgroup, K split over its four waves (linear_small_kernel)
+bool plan_small(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
+    if (!(k.small && k.force_cfg == CFG_AUTO && !p.x6 && d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad == 0 && d.h == d.ho && d.w == d.wo &&
+          !d.out_nchw && !a.mask && !a.cls_mode && !a.bn_part && d.res_mode != EGR_RES_UP2_BEFORE_ACT && a.K % 32 == 0 && a.K <= k.small_k &&
+          d.split_k <= 1 && (int64_t)a.M * d.groups <= k.small_rows))
+        return false;
+    const int64_t tiles = (int64_t)((a.M + 31) / 32) * (a.Npad / 32);
+    // (measured inside a hipGraph, per launch: 64 tiles K 128 4.1 us against 6.5 tiled, 256 tiles K 512 12.2 against 16.2, 1024 tiles
+    // K 64 6.0 against 10.6 - but 1024 tiles K 128 25 against 12, and M 32 x K 32768 0.34 ms against 0.11 with split-K)
+    if (!(tiles * d.groups <= k.small_tiles || a.K <= 64)) return false;
+    out = plan_tile(p, EGR_ROUTE_SMALL_F32, 32, 32, 0, 256);
+    return true;
+}
 
+// 3x3 / stride 1 / pad 1 split launches whose tiles are whole image rows: the tap-sharing kernel
+bool plan_tap(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
+    if (!(k.tap && k.force_cfg == CFG_AUTO && p.x6 && d.kh == 3 && d.kw == 3 && d.stride == 1 && d.pad == 1 &&
+          !a.cls_mode && d.split_k <= 1 && (d.wo == 8 || d.wo == 16 || d.wo == 32 || d.wo == 64) && d.ho == d.h && d.wo == d.w &&
+          a.Npad % 64 == 0 && a.M >= 2048))
+        return false;
+    // 256 x 64 tiles for 64 / 192 output channels (as many MFMAs per tap as 128 x 128), 128 x 128 when that fills the chip, else 128 x 64
+    const int P = d.ho * d.wo;
+    auto fits_tile = [&](int bm) {
+        if (a.M % bm != 0 || !((P % bm == 0) || (bm % P == 0))) return false;
+        const int hp = P >= bm ? (bm / d.wo + 2) * (d.wo + 2) : (bm / P) * (d.ho + 2) * (d.wo + 2);
+        return hp <= tap_hpmax(bm);
+    };
+    int bm = 0, bn = 0;
+    if (a.Npad % 128 == 0 && fits_tile(128) && (int64_t)(a.M / 128) * (a.Npad / 128) * d.groups >= 256) { bm = 128; bn = 128; }
+    else if (fits_tile(256) && (int64_t)(a.M / 256) * (a.Npad / 64) * d.groups >= 256) { bm = 256; bn = 64; }
+    else if (fits_tile(128)) { bm = 128; bn = 64; }
+    // few rows (batch 1: layer1 has 128 tiles of 128 x 64, layer2 64): 64-row tiles put twice the workgroups on the chip
+    if (k.tap64 && p.h2 && bm == 128 && bn == 64 && !a.bn_part && fits_tile(64) && (int64_t)(a.M / 128) * (a.Npad / 64) * d.groups < 256) bm = 64;
+    if (!bm) return false;
+    out = plan_tile(p, EGR_ROUTE_TAP, bm, bn, 0, 256);
+    return true;
+}
+
+// 3x3 / stride 2 / pad 1 split launches on even images: taps shared by parity class
+bool plan_tap2(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
+    if (!(k.tap && k.tap2 && k.force_cfg == CFG_AUTO && p.x6 && d.kh == 3 && d.kw == 3 && d.stride == 2 && d.pad == 1 &&
+          !d.transposed && !a.cls_mode && d.split_k <= 1 && !a.mask && (d.wo == 8 || d.wo == 16 || d.wo == 32) &&
+          d.h == 2 * d.ho && d.w == 2 * d.wo && a.Npad % 64 == 0 && a.M >= 2048 && a.M % 128 == 0))
+        return false;
+    const int P = d.ho * d.wo;
+    const int hp = P >= 128 ? (128 / d.wo + 1) * (d.wo + 1) : (128 / P) * (d.ho + 1) * (d.wo + 1);
+    if (!(((P % 128 == 0) || (128 % P == 0)) && hp <= 192)) return false;
+    const int bn = (a.Npad % 128 == 0 && (int64_t)(a.M / 128) * (a.Npad / 128) * d.groups >= 256) ? 128 : 64;
+    out = plan_tile(p, EGR_ROUTE_TAP2, 128, bn, 0, 256);
+    return true;
+}
+
+// 1x1 / stride 1 split launches with cin = 64 / 128 over many pixels: weights stationary in LDS, activations streamed
+bool plan_stream(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
+    if (!(k.tap && k.pw && !a.bn_part && k.force_cfg == CFG_AUTO && p.x6 && d.kh == 1 && d.kw == 1 && d.pad == 0 &&
+          (d.stride == 1 || (d.stride == 2 && !d.transposed && d.ho == (d.h - 1) / 2 + 1 && d.wo == (d.w - 1) / 2 + 1)) &&
+          !a.cls_mode && d.split_k <= 1 && !d.out_nchw && !a.rowscale && !a.rowmask && a.vec_ok && d.cout % 4 == 0 &&
+          d.act != EGR_ACT_GELU && (d.cin == 64 || d.cin == 128) && a.Npad % 64 == 0 && (d.stride == 2 || (d.h == d.ho && d.w == d.wo)) &&
+          (int64_t)a.M * d.groups >= k.pw_min_rows && p.yspan * 4 < (1LL << 31) && (!d.res_mode || p.rspan * 4 < (1LL << 31))))
+        return false;
+    const int ncf = (a.Npad % 128 == 0) ? 4 : 2;
+    const int resk = d.res_mode == EGR_RES_NONE ? 0 : (d.res_mode == EGR_RES_UP2_BEFORE_ACT ? 2 : 1);
+    egr_conv_plan_t pl = plan_tile(p, EGR_ROUTE_STREAM_1X1, 32, ncf * 32, 100 * (d.cin / 16) + 10 * ncf + resk, 512);
+    // `pw_blocks` resident workgroups, each walking 32-row steps eight at a time (one per wave) down its column of tiles
+    int nblk = k.pw_blocks / (pl.tiles_n * d.groups);
+    if (nblk < 1) nblk = 1;
+    if (nblk * 8 > pl.tiles_m) nblk = (pl.tiles_m + 7) / 8;
+    pl.grid_x = nblk; pl.grid_y = pl.tiles_n;
+    pl.persistent = 1;
+    out = pl;
+    return true;
+}
+
+// everything else: one BM x BN tile per workgroup on the fp32 or the 16-bit matrix cores, split-K for skinny GEMMs with long K,
+// persistent workgroups for short K.  Always takes the problem; returns the EGR_E* code of a split that cannot run.
+int plan_tiled(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
     // ---- tile configuration
-    int cfg = g_force_cfg;
+    int cfg = k.force_cfg;
     if (cfg == CFG_AUTO) {
         if (a.Npad == 32) cfg = CFG_128x32;
         else if (a.M <= 4096) cfg = CFG_64x64;
-        else if (x6) {
+        else if (p.x6) {
             // split-bf16 launches: a stage is only 6 MFMAs per 32x32 fragment, so the wave tile must be at least 64x32 to keep
             // the barrier count down (N = 64 / 192: 128x64, measured 123 vs 94 TF on 64x64), and 128x128 needs two resident
             // workgroups per CU to overlap its barriers (layer4 alone: 256 workgroups ran 91 TF, as 128x64 121 TF)
@@ -2452,87 +2418,226 @@ static int conv_run(const egr_conv_desc* dd, const float* x, const float* w, con
         } else if (a.Npad % 128 == 0) cfg = CFG_128x128;
         else cfg = CFG_64x64;  // N = 64 / 192: 128x64 wins the isolated micro-benchmark (+15 %) but not the pipeline (26.2 vs 26.0 ms); 256x64 runs at 1 workgroup/CU
     }
-    const int bm = kBM[cfg], bn = kBN[cfg];
+    egr_conv_plan_t pl = plan_tile(p, p.x6 ? EGR_ROUTE_SPLIT_TILED : EGR_ROUTE_F32_TILED, kBM[cfg], kBN[cfg], cfg, 256);
 
     // ---- split-K: auto (0) fills the chip for skinny GEMMs with long K
-    int blocks = ((a.M + bm - 1) / bm) * ((a.Npad + bn - 1) / bn) * d.groups;
-    if (a.cls_mode) d.split_k = 1;
-    if (d.split_k <= 0) {
-        d.split_k = 1;
+    const int blocks = pl.tiles_m * pl.tiles_n * d.groups;
+    int split = a.cls_mode ? 1 : d.split_k;
+    if (split <= 0) {
+        split = 1;
         // (also: a few hundred blocks each walking a very long K alone - heatmap_proj.0: 240 blocks x 128 chunks, latency-bound)
         // (small batches: 128 .. 511 blocks walking 18+ chunks alone leave most CUs idle and are latency-bound as well - layer1 / layer2 at
         // batch 1: 42 -> ~25 us with the K range split 2-4 ways)
-        static const int mid_kt = getenv("EGR_SPLITK_MID_KT") ? atoi(getenv("EGR_SPLITK_MID_KT")) : 16;   // tuning knob
-        if ((blocks < 128 ? a.ktiles >= 32 : (blocks < 512 && !x6 && (a.ktiles >= 64 || (mid_kt > 0 && a.ktiles >= mid_kt)))) && workspace) {
+        if ((blocks < 128 ? a.ktiles >= 32 : (blocks < 512 && !p.x6 && (a.ktiles >= 64 || (k.splitk_mid_kt > 0 && a.ktiles >= k.splitk_mid_kt)))) && a.ws) {
             // skinny GEMM streaming a long weight matrix (mlp_pred.0: 268 MB): a block's two-stage pipeline moves ~8 GB/s,
             // so the HBM rate is set by how many blocks stream at once -> aim at 4 per CU
-            static const int target = getenv("EGR_SPLITK_TARGET") ? atoi(getenv("EGR_SPLITK_TARGET")) : 1024;   // tuning knob
-            int s = target / blocks;
+            int s = k.splitk_target / blocks;
             if (s > a.ktiles / 8) s = a.ktiles / 8;
             if (s > 32) s = 32;
-            while (s > 1 && (size_t)s * a.M * a.Npad * d.groups > workspace_floats) --s;
-            if (s > 1) d.split_k = s;
+            while (s > 1 && (size_t)s * a.M * a.Npad * d.groups > p.workspace_floats) --s;
+            if (s > 1) split = s;
         }
     }
-    if (d.split_k > a.ktiles) d.split_k = a.ktiles;
-    if (d.split_k > 1) {
-        if (!workspace) return EGR_ENULL;
-        if ((size_t)d.split_k * a.M * a.Npad * d.groups > workspace_floats) return EGR_EWORKSPACE;
-        if ((uintptr_t)workspace & 15) return EGR_EINVAL;
+    if (split > a.ktiles) split = a.ktiles;
+    if (split > 1) {
+        if (!a.ws) return EGR_ENULL;
+        if ((size_t)split * a.M * a.Npad * d.groups > p.workspace_floats) return EGR_EWORKSPACE;
+        if (!p.workspace_aligned) return EGR_EINVAL;
     }
-    a.ktiles_per_split = (a.ktiles + d.split_k - 1) / d.split_k;
-    d.split_k = (a.ktiles + a.ktiles_per_split - 1) / a.ktiles_per_split;  // no empty splits
+    pl.ktiles_per_split = (a.ktiles + split - 1) / split;
+    pl.split_k = (a.ktiles + pl.ktiles_per_split - 1) / pl.ktiles_per_split;  // no empty splits
+    pl.grid_y = a.cls_mode ? 4 : pl.split_k;
 
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    a.cnt = nullptr;
-    {
-        const int64_t tiles_all = (int64_t)((a.M + bm - 1) / bm) * ((a.Npad + bn - 1) / bn) * d.groups;
-        if (d.split_k > 1 && g_splitk_fused && tiles_all <= SPLITK_REGION) {
-            static int* base = nullptr;
-            if (!base && hipGetSymbolAddress(reinterpret_cast<void**>(&base), HIP_SYMBOL(g_splitk_cnt)) != hipSuccess) base = nullptr;
-            const int region = base ? splitk_region_of(workspace) : -1;
-            if (region >= 0) a.cnt = base + region * SPLITK_REGION;
+    // ---- persistent launch (short K: a tile is mostly fixed cost and HBM traffic): as many workgroups as stay resident (2 per CU,
+    // launch bounds), each walking `rounds` tiles; a multiple of 8 so that a workgroup's tiles keep its XCD (the tile order hands each
+    // XCD a contiguous run)
+    if (p.x6 && k.persist && pl.bm * pl.bn > 128 * 64 && a.ktiles <= k.persist_ktiles) {
+        const int slots = (k.persist / (pl.grid_y * d.groups)) & ~7;
+        if (slots >= 8 && pl.grid_x > slots) {
+            const int rounds = (pl.grid_x + slots - 1) / slots;
+            pl.grid_x = ((pl.grid_x + rounds - 1) / rounds + 7) & ~7;
+            pl.persistent = 1;
         }
     }
-    switch (cfg) {
-        case CFG_128x128: rc = launch_cfg<128, 128, 2, 2>(a, s); break;
-        case CFG_256x64: rc = launch_cfg<256, 64, 4, 1>(a, s); break;
-        case CFG_64x64: rc = launch_cfg<64, 64, 2, 2>(a, s); break;
-        case CFG_128x64: rc = launch_cfg<128, 64, 2, 2>(a, s); break;
-        default: rc = launch_cfg<128, 32, 4, 1>(a, s); break;
+    // (short K: never split in practice) the persistent tile loop keeps the two-pass reduction
+    pl.fused_reduce = pl.split_k > 1 && k.splitk_fused && !pl.persistent && (int64_t)pl.tiles_m * pl.tiles_n * d.groups <= SPLITK_REGION;
+    pl.reduce_pass = pl.split_k > 1 && !pl.fused_reduce;
+    out = pl;
+    return 0;
+}
+
+int conv_plan(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    if (!(plan_small(p, k, out) || plan_tapx(p, k, out) || plan_tap(p, k, out) || plan_tap2(p, k, out) || plan_stream(p, k, out)))
+        if (const int rc = plan_tiled(p, k, out)) return rc;
+    // the statistics slabs (one per M tile of the height just chosen) must fit the caller's buffer
+    if (p.a.bn_part && (size_t)p.a.d.groups * out.tiles_m * 3 * p.a.d.cout > p.a.bn_cap) return EGR_EWORKSPACE;
+    return 0;
+}
+
+// ---- 4. launch
+
+// the one place the operand format (planes per operand: 2 fp16, 3 bf16) becomes a template argument
+template <class F>
+bool by_planes(int planes, F f) {
+    if (planes == 2) return f(std::integral_constant<int, 2>{});
+    if (planes == 3) return f(std::integral_constant<int, 3>{});
+    return false;
+}
+
+// the tiled routes' kernels of one tile configuration: fp32, split, split persistent (big tiles only)
+template <int BM, int BN, int WM, int WN, class Go>
+bool go_tiled(const egr_conv_plan_t& pl, Go go) {
+    if (pl.route == EGR_ROUTE_F32_TILED) return !pl.persistent && go(conv_igemm_kernel<BM, BN, WM, WN>);
+    return by_planes(pl.planes, [&](auto npl) {
+        constexpr int NPL = decltype(npl)::value;
+        if constexpr (BM * BN > 128 * 64)
+            if (pl.persistent) return go(conv_igemm_x6p_kernel<BM, BN, WM, WN, NPL>);
+        return !pl.persistent && go(conv_igemm_x6_kernel<BM, BN, WM, WN, NPL>);
+    });
+}
+
+// Every kernel of this file a plan can name, by (route, tile, variant, planes); EGR_EINVAL for a plan that names none.
+int launch_conv(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t s) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z), dim3((unsigned)pl.block), 0, s, a);
+        return true;
+    };
+    const int tile = pl.bm * 1000 + pl.bn;
+    bool ok = false;
+    switch (pl.route) {
+        case EGR_ROUTE_SMALL_F32: ok = go(linear_small_kernel); break;
+        case EGR_ROUTE_F32_TILED:
+        case EGR_ROUTE_SPLIT_TILED:
+            switch (pl.variant) {
+                case CFG_128x128: ok = go_tiled<128, 128, 2, 2>(pl, go); break;
+                case CFG_256x64: ok = go_tiled<256, 64, 4, 1>(pl, go); break;
+                case CFG_64x64: ok = go_tiled<64, 64, 2, 2>(pl, go); break;
+                case CFG_128x32: ok = go_tiled<128, 32, 4, 1>(pl, go); break;
+                case CFG_128x64: ok = go_tiled<128, 64, 2, 2>(pl, go); break;
+            }
+            break;
+        case EGR_ROUTE_TAP:
+            if (tile == 64064) ok = pl.planes == 2 && go(conv_igemm_tap_kernel<64, 64, 2, 2, 2>);      // (fp16 scheme only)
+            else ok = by_planes(pl.planes, [&](auto npl) {
+                constexpr int NPL = decltype(npl)::value;
+                switch (tile) {
+                    case 256064: return go(conv_igemm_tap_kernel<256, 64, 4, 1, NPL>);
+                    case 128128: return go(conv_igemm_tap_kernel<128, 128, 2, 2, NPL>);
+                    case 128064: return go(conv_igemm_tap_kernel<128, 64, 2, 2, NPL>);
+                    default: return false;
+                }
+            });
+            break;
+        case EGR_ROUTE_TAP2:
+            ok = by_planes(pl.planes, [&](auto npl) {
+                constexpr int NPL = decltype(npl)::value;
+                switch (tile) {
+                    case 128128: return go(conv_igemm_tap2_kernel<128, 128, 2, 2, NPL>);
+                    case 128064: return go(conv_igemm_tap2_kernel<128, 64, 2, 2, NPL>);
+                    default: return false;
+                }
+            });
+            break;
+        case EGR_ROUTE_STREAM_1X1:
+            ok = by_planes(pl.planes, [&](auto npl) {
+                constexpr int NPL = decltype(npl)::value;
+                switch (pl.variant) {      // 100 KS + 10 NCF + RESK
+                    case 420: return go(conv_pw_x6_kernel<4, 2, 0, NPL>);
+                    case 421: return go(conv_pw_x6_kernel<4, 2, 1, NPL>);
+                    case 422: return go(conv_pw_x6_kernel<4, 2, 2, NPL>);
+                    case 440: return go(conv_pw_x6_kernel<4, 4, 0, NPL>);
+                    case 441: return go(conv_pw_x6_kernel<4, 4, 1, NPL>);
+                    case 442: return go(conv_pw_x6_kernel<4, 4, 2, NPL>);
+                    case 820: return go(conv_pw_x6_kernel<8, 2, 0, NPL>);
+                    case 821: return go(conv_pw_x6_kernel<8, 2, 1, NPL>);
+                    case 822: return go(conv_pw_x6_kernel<8, 2, 2, NPL>);
+                    case 840: return go(conv_pw_x6_kernel<8, 4, 0, NPL>);
+                    case 841: return go(conv_pw_x6_kernel<8, 4, 1, NPL>);
+                    case 842: return go(conv_pw_x6_kernel<8, 4, 2, NPL>);
+                    default: return false;
+                }
+            });
+            break;
     }
-    if (rc) return rc;
-    if (d.split_k > 1 && !a.cnt) {
-        int64_t total = (int64_t)a.M * d.cout;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 256 * SPLITK_RED_EPT - 1) / (256 * SPLITK_RED_EPT)), (unsigned)d.groups), dim3(256), 0, s, a);
+    if (!ok) return EGR_EINVAL;
+    int rc = egr_launch_status();
+    if (rc == 0 && pl.split_k > 1 && !a.cnt) {     // the reduction pass of a split launch
+        const int64_t total = (int64_t)a.M * a.d.cout;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 256 * SPLITK_RED_EPT - 1) / (256 * SPLITK_RED_EPT)), (unsigned)a.d.groups), dim3(256), 0, s, a);
         rc = egr_launch_status();
     }
     return rc;
+}
+
+// applies the plan to the launch arguments, then launches it
+int conv_launch(const egr_conv_plan_t& pl, ConvArgs& a, hipStream_t s) {
+    a.d.split_k = pl.split_k;
+    a.ktiles_per_split = pl.ktiles_per_split;
+    a.tilesM = pl.tiles_m;
+    a.tilesN = pl.tiles_n;
+    a.dTilesN = make_fastdiv(a.tilesN);
+    a.ntiles = a.tilesM * a.tilesN;
+    a.cnt = nullptr;
+    if (pl.fused_reduce) {      // the arrival counters of this workspace (needs the device); none left: the reduction pass
+        static int* base = nullptr;
+        if (!base && hipGetSymbolAddress(reinterpret_cast<void**>(&base), HIP_SYMBOL(g_splitk_cnt)) != hipSuccess) base = nullptr;
+        const int region = base ? splitk_region_of(a.ws) : -1;
+        if (region >= 0) a.cnt = base + region * SPLITK_REGION;
+    }
+    if (a.bn_part) *a.bn_tiles_host = pl.bn_slabs;
+    g_last_conv_kernel = pl.route;
+    return pl.route == EGR_ROUTE_TAPX ? launch_tapx(pl, a, s) : launch_conv(pl, a, s);
+}
+
+int conv_run(const egr_conv_desc* dd, const ConvOperands& o, egr_conv_plan_t* plan_only, void* stream) {
+    if (!dd) return EGR_ENULL;
+    if (const int rc = conv_check(*dd, o)) return rc;
+    ConvArgs a;
+    conv_geometry(a, *dd, o, g_dbg);
+    const bool h2 = a.d.w_format == EGR_W_F16X2;
+    const ConvProblem p = {a, y_span(a.d), a.d.res_mode ? r_span(a.d) : 0, o.workspace_floats, ((uintptr_t)o.workspace & 15) == 0,
+                           h2 || a.d.w_format == EGR_W_BF16X3, h2};
+    egr_conv_plan_t pl;
+    if (const int rc = conv_plan(p, g_knobs, pl)) return rc;
+    if (plan_only) {
+        *plan_only = pl;
+        return 0;
+    }
+    return conv_launch(pl, a, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int egr_conv_plan(const egr_conv_desc* dd, const float* x, const void* w, const float* scale, const float* shift, const float* res,
+                             const float* rowscale, const uint8_t* rowmask, const float* mask, const float* y, const float* workspace,
+                             size_t workspace_floats, const egr_conv_aux* aux, egr_conv_plan_t* out) {
+    if (!out) return EGR_ENULL;
+    return conv_run(dd, {x, static_cast<const float*>(w), scale, shift, res, rowscale, rowmask, mask, const_cast<float*>(y),
+                         const_cast<float*>(workspace), workspace_floats, aux}, out, nullptr);
 }
 
 extern "C" int egr_conv2d_nhwc_f32(const egr_conv_desc* dd, const float* x, const float* w, const float* scale,
                                    const float* shift, const float* res, const float* rowscale,
                                    const uint8_t* rowmask, float* y, float* workspace, size_t workspace_floats,
                                    void* stream) {
-    return conv_run(dd, x, w, scale, shift, res, rowscale, rowmask, nullptr, y, workspace, workspace_floats, nullptr, stream);
+    return conv_run(dd, {x, w, scale, shift, res, rowscale, rowmask, nullptr, y, workspace, workspace_floats, nullptr}, nullptr, stream);
 }
 
 extern "C" int egr_conv2d_nhwc_ex_f32(const egr_conv_desc* dd, const float* x, const void* w, const float* scale,
                                       const float* shift, const float* res, const float* rowscale,
                                       const uint8_t* rowmask, float* y, float* workspace, size_t workspace_floats,
                                       const egr_conv_aux* aux, void* stream) {
-    return conv_run(dd, x, static_cast<const float*>(w), scale, shift, res, rowscale, rowmask, nullptr, y, workspace, workspace_floats, aux, stream);
+    return conv_run(dd, {x, static_cast<const float*>(w), scale, shift, res, rowscale, rowmask, nullptr, y, workspace, workspace_floats, aux}, nullptr, stream);
 }
 
 extern "C" int egr_conv2d_masked_f32(const egr_conv_desc* dd, const float* x, const float* w, const float* res, const float* mask,
                                      float* y, float* workspace, size_t workspace_floats, void* stream) {
     if (!mask) return EGR_ENULL;
-    return conv_run(dd, x, w, nullptr, nullptr, res, nullptr, nullptr, mask, y, workspace, workspace_floats, nullptr, stream);
+    return conv_run(dd, {x, w, nullptr, nullptr, res, nullptr, nullptr, mask, y, workspace, workspace_floats, nullptr}, nullptr, stream);
 }
 
 extern "C" int egr_conv2d_masked_ex_f32(const egr_conv_desc* dd, const float* x, const void* w, const float* res, const float* mask, float* y,
                                         float* workspace, size_t workspace_floats, const egr_conv_aux* aux, void* stream) {
     if (!mask) return EGR_ENULL;
-    return conv_run(dd, x, static_cast<const float*>(w), nullptr, nullptr, res, nullptr, nullptr, mask, y, workspace, workspace_floats, aux, stream);
+    return conv_run(dd, {x, static_cast<const float*>(w), nullptr, nullptr, res, nullptr, nullptr, mask, y, workspace, workspace_floats, aux}, nullptr, stream);
 }

@@ -67,17 +67,9 @@ struct ConvArgs {
     // and min / max (float) of the rows it stores - the slab layout of egr_bn_stats_f32's first pass with one slab per M tile:
     // bn_part [groups][tilesM][2][cout] doubles, then [groups][tilesM][2][cout] floats
     double* bn_part;
-    int* bn_tiles_host;      // HOST pointers (conv_run): where the launch reports its M tiles per group, capacity of bn_part in doubles
+    int* bn_tiles_host;      // HOST pointer (conv_launch): where the launch reports its M tiles per group; capacity of bn_part in doubles
     size_t bn_cap;
 };
-
-// host side, wherever a launch path has fixed its tile height: report the slab count and check the partials fit
-static inline int bn_slabs(const ConvArgs& a) {
-    if (!a.bn_part) return 0;
-    if ((size_t)a.d.groups * a.tilesM * 3 * a.d.cout > a.bn_cap) return EGR_EWORKSPACE;
-    *a.bn_tiles_host = a.tilesM;
-    return 0;
-}
 
 constexpr int BK = 32;
 
@@ -181,10 +173,49 @@ __device__ __forceinline__ void* uniform_ptr(const void* p) {
     return (void*)(((uint64_t)hi << 32) | lo);
 }
 
-// ---- egr_conv_tapx.hip: role-split persistent workgroups for the fp16 scheme's 3x3 forward launches
-constexpr int TAPX_NO = -1000;    // tapx_try: not a launch this kernel covers, nothing was launched
-// yspan / rspan: furthest float a (group's) output / residual access can touch - the epilogue addresses them with 32-bit byte offsets
-int tapx_try(ConvArgs& a, int64_t yspan_floats, int64_t rspan_floats, hipStream_t stream);
-int tapx_set(int on, int min_tiles, int blocks);
+// ---- host side of the dispatch: check -> geometry -> plan -> launch (egr_conv.hip: conv_run)
+
+// tile configurations of the tiled routes (egr_conv_force_config numbering)
+enum { CFG_AUTO = -1, CFG_128x128 = 0, CFG_256x64 = 1, CFG_64x64 = 2, CFG_128x32 = 3, CFG_128x64 = 4, CFG_COUNT = 5 };
+
+// Every knob of the conv dispatch: one record, read from the environment once (load_conv_knobs, egr_conv.hip - the list of names,
+// defaults and meanings), written afterwards only by the egr_conv_set_* / egr_conv_force_config entry points.
+struct ConvKnobs {
+    int tap, tap2, tap64, tap64_env, pw, pw_min_rows, pw_blocks;
+    int small, small_k, small_tiles, small_rows;
+    int persist, persist_ktiles, force_cfg;
+    int splitk_fused, splitk_mid_kt, splitk_target;
+    int tapx, tapx_min_tiles, tapx_blocks, tapx_pw, tapx_tpw, tapx_train, tapx_fn;
+};
+
+// What a plan function may read.  `a` is the checked descriptor with its geometry (conv_geometry); of the data pointers in it only
+// NULL-ness counts (alignment has been folded into vec_ok), `a.dbg` is the debug-stamp buffer at the time of the call.
+struct ConvProblem {
+    const ConvArgs& a;
+    int64_t yspan, rspan;        // furthest float a (group's) output / residual access can touch (rspan 0 without residual)
+    size_t workspace_floats;
+    bool workspace_aligned;      // a.ws is 16-byte aligned
+    bool x6, h2;                 // split kernels (bf16 x 3 / fp16 x 2); h2: the fp16 scheme
+};
+
+// A route has fixed its tile: the fields every route fills the same way (one workgroup per tile until the route says otherwise).
+inline egr_conv_plan_t plan_tile(const ConvProblem& p, int route, int bm, int bn, int variant, int block) {
+    const ConvArgs& a = p.a;
+    egr_conv_plan_t pl = {};
+    pl.route = route; pl.bm = bm; pl.bn = bn; pl.variant = variant;
+    pl.planes = p.h2 ? 2 : (p.x6 ? 3 : 0);
+    pl.tiles_m = (a.M + bm - 1) / bm;
+    pl.tiles_n = (a.Npad + bn - 1) / bn;
+    pl.grid_x = pl.tiles_m * pl.tiles_n; pl.grid_y = 1; pl.grid_z = a.d.groups;
+    pl.block = block;
+    pl.split_k = 1; pl.ktiles_per_split = a.ktiles;
+    pl.cls_mode = a.cls_mode;
+    pl.bn_slabs = a.bn_part ? pl.tiles_m : 0;
+    return pl;
+}
+
+// egr_conv_tapx.hip: role-split persistent workgroups for the fp16 scheme's 3x3 (and wide 1x1) launches
+bool plan_tapx(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out);
+int launch_tapx(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t stream);    // EGR_EINVAL: no such variant
 
 }  // namespace egrc

@@ -637,48 +637,46 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
     }
 }
 
-int g_tapx = getenv("EGR_CONV_TAPX") ? atoi(getenv("EGR_CONV_TAPX")) : 1;                          // 0: the 3x3 launches stay on conv_igemm_tap[2]_kernel
-int g_tapx_min_tiles = getenv("EGR_CONV_TAPX_MIN_TILES") ? atoi(getenv("EGR_CONV_TAPX_MIN_TILES")) : 256; // tiles (all groups) from which the role-split kernel is used
-int g_tapx_blocks = getenv("EGR_CONV_TAPX_BLOCKS") ? atoi(getenv("EGR_CONV_TAPX_BLOCKS")) : 256;    // resident workgroups (one per CU)
-int g_tapx_pw = getenv("EGR_CONV_TAPX_PW") ? atoi(getenv("EGR_CONV_TAPX_PW")) : 1;                  // 0: 1x1 launches with >= 256 input channels stay on the tiled kernel
-int g_tapx_tpw = getenv("EGR_CONV_TAPX_TPW") ? atoi(getenv("EGR_CONV_TAPX_TPW")) : 0;               // > 0: tiles per workgroup of a non-persistent launch (experiment)
-int g_tapx_train = getenv("EGR_CONV_TAPX_TRAIN") ? atoi(getenv("EGR_CONV_TAPX_TRAIN")) : 1;         // 0: statistics-epilogue / masked launches stay on conv_igemm_tap_kernel
-int g_tapx_fn = getenv("EGR_CONV_TAPX_FN") ? atoi(getenv("EGR_CONV_TAPX_FN")) : 0;                  // wave tile: 0 by shape, 1: 128 x 32, 2: 128 x 64 wherever it exists
-
 }  // namespace
 
 namespace egrc {
 
-int tapx_set(int on, int min_tiles, int blocks) {
-    if (on >= 0) { g_tapx = on != 0; g_tapx_fn = on >= 2 ? on - 1 : 0; }      // on = 2 / 3: the 128 x 32 / 128 x 64 wave tile wherever it exists (tests)
-    if (min_tiles >= 0) g_tapx_min_tiles = min_tiles;
-    if (blocks > 0) g_tapx_blocks = blocks;
-    return 0;
-}
+namespace {
+// conv_tapx_kernel configurations: tile rows x columns, and which of them exist with a training epilogue (TR 1: statistics, 2: masked).
+// Forward (TR 0) every configuration exists, with and without residual.
+const int kTapxBM[8] = {256, 128, 512, 256, 128, 128, 128, 128}, kTapxBN[8] = {128, 128, 64, 64, 256, 128, 256, 128};
+const bool kTapxTrain[3][8] = {{true, true, false, true, true, true, true, true},
+                               {true, true, false, true, false, true, false, false},
+                               {false, true, false, true, false, false, false, false}};
+}  // namespace
 
-// Launch conv_tapx_kernel if the problem is one it covers: returns TAPX_NO (nothing launched) or the launch status.
-// `a` arrives from conv_run with the geometry fields filled in (M, Npad, K, cblocks, ktiles, *_shift, *_plain, vec_ok, cls_mode).
-int tapx_try(ConvArgs& a, int64_t yspan_floats, int64_t rspan_floats, hipStream_t stream) {
-    egr_conv_desc& d = a.d;
+// The decision half of the role-split route: fills `out` if conv_tapx_kernel covers the problem, else leaves it untouched.
+// p.a carries the geometry (M, Npad, K, cblocks, ktiles, *_shift, *_plain, vec_ok, cls_mode).
+bool plan_tapx(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    const ConvArgs& a = p.a;
+    const egr_conv_desc& d = a.d;
     const bool pw = d.kh == 1 && d.kw == 1;
-    if (!g_tapx || d.w_format != EGR_W_F16X2 || !(pw ? (d.pad == 0 && d.stride == 1 && g_tapx_pw) : (d.kh == 3 && d.kw == 3 && d.pad == 1)) ||
+    // the fp16 scheme's 3x3 (and wide 1x1) launches with enough tiles - forward, and the training step's statistics-epilogue and
+    // stride-1 data-gradient (plain / masked) ones
+    if (!(k.tap && k.force_cfg == CFG_AUTO && p.h2 && ((d.kh == 3 && d.kw == 3) || (pw && d.cin >= 256)))) return false;
+    if (!k.tapx || d.w_format != EGR_W_F16X2 || !(pw ? (d.pad == 0 && d.stride == 1 && k.tapx_pw) : (d.kh == 3 && d.kw == 3 && d.pad == 1)) ||
         (d.transposed && (pw || d.stride != 1)) || a.cls_mode || d.split_k > 1 ||
         d.out_nchw || a.rowscale || a.rowmask || (a.mask && a.bn_part) || !a.vec_ok || d.cout % 4 != 0 || d.cin < 64 ||
         (d.act != EGR_ACT_NONE && d.act != EGR_ACT_RELU) || d.res_mode == EGR_RES_UP2_BEFORE_ACT || (a.dbg && !TAPX_DBG))
-        return TAPX_NO;
-    if (yspan_floats * 4 >= (1LL << 31) || (d.res_mode && rspan_floats * 4 >= (1LL << 31))) return TAPX_NO;   // 32-bit byte offsets in the epilogue
+        return false;
+    if (p.yspan * 4 >= (1LL << 31) || (d.res_mode && p.rspan * 4 >= (1LL << 31))) return false;   // 32-bit byte offsets in the epilogue
     // training launches (statistics epilogue: raw output of a 3x3 conv; masked data gradient: 3x3 / stride 1): the narrow wave tile
     const int tr = a.bn_part ? 1 : (a.mask ? 2 : 0);
-    if (tr && (pw || !g_tapx_train)) return TAPX_NO;
-    if (tr == 1 && (d.act != EGR_ACT_NONE || d.res_mode != EGR_RES_NONE || d.transposed || d.cout % 64 != 0)) return TAPX_NO;
-    if (tr == 2 && (d.stride != 1 || a.scale || a.shift || d.act != EGR_ACT_NONE || d.res_mode == EGR_RES_AFTER_ACT)) return TAPX_NO;
+    if (tr && (pw || !k.tapx_train)) return false;
+    if (tr == 1 && (d.act != EGR_ACT_NONE || d.res_mode != EGR_RES_NONE || d.transposed || d.cout % 64 != 0)) return false;
+    if (tr == 2 && (d.stride != 1 || a.scale || a.shift || d.act != EGR_ACT_NONE || d.res_mode == EGR_RES_AFTER_ACT)) return false;
     // (the wide wave tile has no registers left for the mask quads; at >= 128 channels the narrow one is no faster than
     // conv_igemm_tap_kernel - 345 against 340 TFLOP/s at 128 channels, 346 against 358 at 256 - so masked launches come here for 64-channel
     // outputs only.  The statistics epilogue exists on both wave tiles for stride 1, on the narrow one for stride 2.)
-    if (tr == 2 && a.Npad % 128 == 0 && g_tapx_train < 2 && g_tapx_min_tiles > 1) return TAPX_NO;     // (forced from one tile up: tests)
-    const int fn = (tr == 2 || (tr == 1 && d.stride == 2)) ? 1 : g_tapx_fn;
+    if (tr == 2 && a.Npad % 128 == 0 && k.tapx_train < 2 && k.tapx_min_tiles > 1) return false;     // (forced from one tile up: tests)
+    const int fn = (tr == 2 || (tr == 1 && d.stride == 2)) ? 1 : k.tapx_fn;
     const int P = d.ho * d.wo;
-    if (a.howo_shift < 0 || a.wo_shift < 0) return TAPX_NO;
+    if (a.howo_shift < 0 || a.wo_shift < 0) return false;
     const int ext = d.stride == 1 ? 2 : 1;
     auto fits = [&](int bm, int bn) {        // tiles of whole image rows / whole small images whose planes fit the kernel's LDS buffers
         if (a.Npad % bn != 0 || a.M % bm != 0) return false;
@@ -693,81 +691,74 @@ int tapx_try(ConvArgs& a, int64_t yspan_floats, int64_t rspan_floats, hipStream_
         // training launches (config 5 at batch 32 has 256-1024 tiles per trunk launch): from four tiles per CU - measured per launch,
         // statistics epilogue, role-split against tap-sharing kernel: 64 channels / 2048 tiles 0.538 against 0.573 ms, 128 channels /
         // 1024 narrow tiles 0.448 against 0.471 (512 wide tiles: 0.478), 256 channels / 512 tiles 0.335-0.349 against 0.324
-        if (tr) return tiles >= 4 * (int64_t)g_tapx_min_tiles || g_tapx_min_tiles <= 1;
+        if (tr) return tiles >= 4 * (int64_t)k.tapx_min_tiles || k.tapx_min_tiles <= 1;
         // below 2048 rows the alternative is the generic split kernel (the tap-sharing ones start there): a quarter of the CUs on this
         // kernel is still faster - the refiners' 256 -> 512 stride-2 conv at batch 1 (128 tiles) 72 us there
-        if (!pw && a.M < 2048 && tiles >= g_tapx_min_tiles / 4 && a.cblocks >= 4) return true;
-        return tiles >= g_tapx_min_tiles && (tiles >= 2 * (int64_t)g_tapx_min_tiles || (!pw && a.cblocks >= 16) || g_tapx_min_tiles <= 1);
+        if (!pw && a.M < 2048 && tiles >= k.tapx_min_tiles / 4 && a.cblocks >= 4) return true;
+        return tiles >= k.tapx_min_tiles && (tiles >= 2 * (int64_t)k.tapx_min_tiles || (!pw && a.cblocks >= 16) || k.tapx_min_tiles <= 1);
     };
     // tiles (rows x columns): the 128 x 64 wave tile (FN = 2) wherever the channel count allows it - stride 1: 256 x 128, stride 2:
     // 128 x 256 - else the 128 x 32 one (FN = 1): stride 1: 256 x 64 (64 / 192 channels; measured in the pipeline at batch 64:
     // layer1 346 TFLOP/s against 291 on conv_igemm_tap_kernel and 245 on 512 x 64 tiles) or 128 x 128, stride 2: 128 x 128
     int cfg = -1;
     if (pw) {      // 1x1 with >= 256 input channels (chunks of 64): 128 x 256 tiles, else 128 x 128
-        if (d.cin % 128 != 0 || d.cin < 256 || d.h != d.ho || d.w != d.wo) return TAPX_NO;      // (an even number of 64-channel chunks, at least four)
-        cfg = (g_tapx_fn != 1 && fits(128, 256)) ? 6 : (g_tapx_fn != 2 && fits(128, 128) ? 7 : (fits(128, 256) ? 6 : -1));
+        if (d.cin % 128 != 0 || d.cin < 256 || d.h != d.ho || d.w != d.wo) return false;      // (an even number of 64-channel chunks, at least four)
+        cfg = (k.tapx_fn != 1 && fits(128, 256)) ? 6 : (k.tapx_fn != 2 && fits(128, 128) ? 7 : (fits(128, 256) ? 6 : -1));
     } else if (d.stride == 1) {
-        if (!(d.wo == 8 || d.wo == 16 || d.wo == 32 || d.wo == 64) || d.ho != d.h || d.wo != d.w) return TAPX_NO;
+        if (!(d.wo == 8 || d.wo == 16 || d.wo == 32 || d.wo == 64) || d.ho != d.h || d.wo != d.w) return false;
         if (a.Npad % 128 == 0) cfg = (fn != 1 && fits(256, 128)) ? 0 : (fn != 2 && fits(128, 128) ? 1 : (fn != 1 && fits(256, 128) ? 0 : -1));
         else cfg = fits(256, 64) ? 3 : -1;
     } else if (d.stride == 2) {
-        if (!(d.wo == 8 || d.wo == 16 || d.wo == 32) || d.h != 2 * d.ho || d.w != 2 * d.wo) return TAPX_NO;
+        if (!(d.wo == 8 || d.wo == 16 || d.wo == 32) || d.h != 2 * d.ho || d.w != 2 * d.wo) return false;
         if (a.M < 2048 && fn == 0) cfg = fits(128, 128) ? 5 : (fits(128, 256) ? 4 : -1);       // (few rows: the narrower tile = twice the workgroups)
         else cfg = (fn != 1 && fits(128, 256)) ? 4 : (fn != 2 && fits(128, 128) ? 5 : (fn != 1 && fits(128, 256) ? 4 : -1));
     }
-    if (cfg < 0) return TAPX_NO;
-    static const int kbm[8] = {256, 128, 512, 256, 128, 128, 128, 128}, kbn[8] = {128, 128, 64, 64, 256, 128, 256, 128};
-    const int bm = kbm[cfg], bn = kbn[cfg];
+    if (cfg < 0 || !kTapxTrain[tr][cfg]) return false;     // (no kernel for this tile / epilogue pair: the caller's other routes take the problem)
+    const int bm = kTapxBM[cfg], bn = kTapxBN[cfg];
     const int64_t tiles = (int64_t)(a.M / bm) * (a.Npad / bn) * d.groups;
-    if (tiles >= (1 << 30)) return TAPX_NO;
-    d.split_k = 1;
-    a.ktiles_per_split = a.ktiles;
-    a.tilesM = a.M / bm;
-    a.tilesN = a.Npad / bn;
-    a.dTilesN = make_fastdiv(a.tilesN);
-    a.ntiles = a.tilesM * a.tilesN;
-    if (const int rcb = bn_slabs(a)) return rcb;
-    // workgroups: one per CU walking tiles / blocks tiles each - or, with g_tapx_tpw > 0 (experiment), more workgroups of about that many
+    if (tiles >= (1 << 30)) return false;
+    // workgroups: one per CU walking tiles / blocks tiles each - or, with tapx_tpw > 0 (experiment), more workgroups of about that many
     // tiles each, handed to CUs as they free up: measured 6647 frames/s persistent, 6588 / 6511-6520 / 6334 with 8 / 4 / 2 tiles per workgroup
-    int64_t wgs = g_tapx_blocks;
-    if (g_tapx_tpw > 0 && tiles / g_tapx_tpw > wgs) wgs = (tiles / g_tapx_tpw + 7) / 8 * 8;
-    const unsigned grid = (unsigned)(tiles < wgs ? tiles : wgs);
-    auto launch = [&](auto res_tag) {
-        constexpr bool R = decltype(res_tag)::value;
-        switch (cfg) {
-            case 0: hipLaunchKernelGGL((conv_tapx_kernel<2, 2, 2, 1, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            case 1: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 1, 1, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            case 3: hipLaunchKernelGGL((conv_tapx_kernel<2, 2, 1, 1, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            case 4: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 2, 2, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            case 5: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 1, 2, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            case 6: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 2, 0, R>), dim3(grid), dim3(512), 0, stream, a); break;
-            default: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 1, 0, R>), dim3(grid), dim3(512), 0, stream, a); break;
-        }
+    int64_t wgs = k.tapx_blocks;
+    if (k.tapx_tpw > 0 && tiles / k.tapx_tpw > wgs) wgs = (tiles / k.tapx_tpw + 7) / 8 * 8;
+    out = plan_tile(p, EGR_ROUTE_TAPX, bm, bn, 100 * tr + 10 * (d.res_mode != EGR_RES_NONE) + cfg, 512);
+    out.grid_x = (int32_t)(tiles < wgs ? tiles : wgs);
+    out.grid_z = 1;
+    out.persistent = tiles > wgs;
+    return true;
+}
+
+// The launch half: one switch over the variants that exist (the table above says which the plan may name).
+int launch_tapx(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t stream) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x), dim3((unsigned)pl.block), 0, stream, a);
+        return egr_launch_status();
     };
-    // (false: no instantiation for this tile / epilogue pair - nothing was launched and the caller's other kernels take the problem)
-    auto launch_tr = [&](auto res_tag, auto tr_tag) -> bool {
-        constexpr bool R = decltype(res_tag)::value;
-        constexpr int T = decltype(tr_tag)::value;
-        switch (cfg) {
-            case 0:
-                if constexpr (T == 1) { hipLaunchKernelGGL((conv_tapx_kernel<2, 2, 2, 1, R, T>), dim3(grid), dim3(512), 0, stream, a); return true; }
-                return false;
-            case 1: hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 1, 1, R, T>), dim3(grid), dim3(512), 0, stream, a); return true;
-            case 3: hipLaunchKernelGGL((conv_tapx_kernel<2, 2, 1, 1, R, T>), dim3(grid), dim3(512), 0, stream, a); return true;
-            case 5:
-                if constexpr (T == 1) { hipLaunchKernelGGL((conv_tapx_kernel<1, 4, 1, 2, R, T>), dim3(grid), dim3(512), 0, stream, a); return true; }
-                return false;
-            default: return false;
-        }
-    };
-    bool launched = true;
-    if (tr == 1) launched = launch_tr(std::false_type{}, std::integral_constant<int, 1>{});
-    else if (tr == 2 && d.res_mode != EGR_RES_NONE) launched = launch_tr(std::true_type{}, std::integral_constant<int, 2>{});
-    else if (tr == 2) launched = launch_tr(std::false_type{}, std::integral_constant<int, 2>{});
-    else if (d.res_mode != EGR_RES_NONE) launch(std::true_type{});
-    else launch(std::false_type{});
-    if (!launched) return TAPX_NO;
-    return egr_launch_status();
+    switch (pl.variant) {    // 100 TR + 10 R + cfg; template arguments <WM, WN, FN, STRIDE (0: 1x1), RES, TR>
+        case 0: return go(conv_tapx_kernel<2, 2, 2, 1, false>);
+        case 1: return go(conv_tapx_kernel<1, 4, 1, 1, false>);
+        case 3: return go(conv_tapx_kernel<2, 2, 1, 1, false>);
+        case 4: return go(conv_tapx_kernel<1, 4, 2, 2, false>);
+        case 5: return go(conv_tapx_kernel<1, 4, 1, 2, false>);
+        case 6: return go(conv_tapx_kernel<1, 4, 2, 0, false>);
+        case 7: return go(conv_tapx_kernel<1, 4, 1, 0, false>);
+        case 10: return go(conv_tapx_kernel<2, 2, 2, 1, true>);
+        case 11: return go(conv_tapx_kernel<1, 4, 1, 1, true>);
+        case 13: return go(conv_tapx_kernel<2, 2, 1, 1, true>);
+        case 14: return go(conv_tapx_kernel<1, 4, 2, 2, true>);
+        case 15: return go(conv_tapx_kernel<1, 4, 1, 2, true>);
+        case 16: return go(conv_tapx_kernel<1, 4, 2, 0, true>);
+        case 17: return go(conv_tapx_kernel<1, 4, 1, 0, true>);
+        case 100: return go(conv_tapx_kernel<2, 2, 2, 1, false, 1>);
+        case 101: return go(conv_tapx_kernel<1, 4, 1, 1, false, 1>);
+        case 103: return go(conv_tapx_kernel<2, 2, 1, 1, false, 1>);
+        case 105: return go(conv_tapx_kernel<1, 4, 1, 2, false, 1>);
+        case 201: return go(conv_tapx_kernel<1, 4, 1, 1, false, 2>);
+        case 203: return go(conv_tapx_kernel<2, 2, 1, 1, false, 2>);
+        case 211: return go(conv_tapx_kernel<1, 4, 1, 1, true, 2>);
+        case 213: return go(conv_tapx_kernel<2, 2, 1, 1, true, 2>);
+        default: return EGR_EINVAL;
+    }
 }
 
 }  // namespace egrc

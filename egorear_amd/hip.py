@@ -137,6 +137,7 @@ EXPORTS = [
     "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2",
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
+    "egr_conv_plan",
 ]
 
 
@@ -162,6 +163,16 @@ class ConvAux(C.Structure):
     """egr_conv_aux of include/egorear_hip.h: side operands of the fp16 scheme (EGR_W_F16X2) and the abs-max record of the output."""
     _fields_ = [("w_descale", C.c_void_p), ("amax_in", C.c_void_p), ("amax_out", C.c_void_p),
                 ("bn_partials", C.c_void_p), ("bn_tiles_out", C.c_void_p), ("bn_capacity", C.c_int64)]
+
+
+class ConvPlan(C.Structure):
+    """egr_conv_plan_t of include/egorear_hip.h: what a conv launch will do (route, tile, variant, grid, split-K, ...)."""
+    _fields_ = [(n, C.c_int32) for n in ("route", "bm", "bn", "variant", "planes", "tiles_m", "tiles_n", "grid_x", "grid_y", "grid_z", "block",
+                                         "split_k", "ktiles_per_split", "persistent", "cls_mode", "fused_reduce", "reduce_pass", "bn_slabs")]
+
+
+# egr_conv_route: the values of ConvPlan.route and of conv_last_kernel()
+ROUTE_F32_TILED, ROUTE_SPLIT_TILED, ROUTE_TAP, ROUTE_TAP2, ROUTE_STREAM_1X1, ROUTE_SMALL_F32, ROUTE_TAPX = range(7)
 
 
 class ChainAux(C.Structure):
@@ -208,6 +219,7 @@ def _load() -> C.CDLL:
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
     lib.egr_conv2d_nhwc_f32.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.egr_conv2d_nhwc_ex_f32.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(ConvAux), vp]
+    lib.egr_conv_plan.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(ConvAux), C.POINTER(ConvPlan)]
     lib.egr_conv1x1_chain_f32.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, C.POINTER(ConvAux), C.POINTER(ChainAux), vp]
     lib.egr_fill_f32.argtypes = [vp, f32, i64, vp]      # (include/egorear_train.h; zeroes the abs-max records)
     lib.egr_fill_f32.restype = C.c_int
@@ -403,6 +415,16 @@ def conv_force_config(cfg: int):
 
 def conv_set_persist(slots: int = -1, max_ktiles: int = -1):
     _check(lib.egr_conv_set_persist(slots, max_ktiles), "egr_conv_set_persist")
+
+
+def conv_plan(d: "ConvDesc", x, w, y, *, scale=None, shift=None, res=None, rowscale=None, rowmask=None, mask=None, workspace=None,
+              workspace_floats: int = 0, aux: Optional["ConvAux"] = None):
+    """(return code, ConvPlan) of egr_conv_plan: what egr_conv2d_nhwc_ex_f32 (mask None) / egr_conv2d_masked_ex_f32 would launch for
+    these arguments.  Operands are raw addresses (ints or None): none is dereferenced and no device is touched."""
+    out = ConvPlan()
+    rc = lib.egr_conv_plan(C.byref(d), x, w, scale, shift, res, rowscale, rowmask, mask, y, workspace, workspace_floats,
+                           C.byref(aux) if aux is not None else None, C.byref(out))
+    return rc, out
 
 
 def device_arch() -> str:

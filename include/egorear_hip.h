@@ -209,6 +209,47 @@ int egr_conv2d_masked_f32(const egr_conv_desc* d, const float* x, const float* w
 int egr_conv2d_masked_ex_f32(const egr_conv_desc* d, const float* x, const void* w, const float* res, const float* mask, float* y,
                              float* workspace, size_t workspace_floats, const egr_conv_aux* aux, void* stream);
 
+/* What a launch of egr_conv2d_nhwc[_ex]_f32 / egr_conv2d_masked[_ex]_f32 will do, decided on the host before anything is launched
+ * (DESIGN.md §5j).  The route values are the codes egr_conv_last_kernel() reports. */
+typedef enum {
+    EGR_ROUTE_F32_TILED = 0,     /* fp32 matrix cores, one BM x BN tile per workgroup (EGR_W_F32) */
+    EGR_ROUTE_SPLIT_TILED = 1,   /* the same tiles on the 16-bit matrix cores (EGR_W_BF16X3 / EGR_W_F16X2), persistent for short K */
+    EGR_ROUTE_TAP = 2,           /* 3x3 / stride 1 / pad 1, tiles of whole image rows: the taps share one staged halo */
+    EGR_ROUTE_TAP2 = 3,          /* 3x3 / stride 2 / pad 1 on even images: taps shared by input parity class (env EGR_CONV_TAP2=0: off) */
+    EGR_ROUTE_STREAM_1X1 = 4,    /* 1x1, cin 64 / 128, many rows: weights stationary in LDS, activations streamed (env EGR_CONV_PW=0: off) */
+    EGR_ROUTE_SMALL_F32 = 5,     /* small fp32 1x1 / stride 1: one 32 x 32 tile per workgroup, K split over its four waves, operands read
+                                  * straight from global memory (env EGR_CONV_SMALL=0: off); sums differ from route 0's in the last bits */
+    EGR_ROUTE_TAPX = 6           /* fp16 scheme, 3x3 and wide 1x1: role-split persistent workgroups (egr_conv_set_tapx) */
+} egr_conv_route;
+typedef struct {
+    int32_t route;               /* egr_conv_route */
+    int32_t bm, bn;              /* tile rows x columns (STREAM_1X1: 32 rows per wave step, NCF * 32 columns) */
+    /* which kernel of the route where the tile does not say it all:
+     *   F32_TILED / SPLIT_TILED  the tile configuration (egr_conv_force_config numbering)
+     *   STREAM_1X1               100 KS + 10 NCF + RESK  (KS = cin / 16, NCF = 32-column fragments per workgroup, RESK 0 no residual /
+     *                            1 residual / 2 residual upsampled on the fly)
+     *   TAPX                     100 T + 10 R + cfg  (T 0 forward / 1 statistics epilogue / 2 masked data gradient, R 1 with residual,
+     *                            cfg = the kernel's (tile, wave tile, stride) configuration 0, 1, 3 .. 7)
+     *   others                   0 */
+    int32_t variant;
+    int32_t planes;              /* 16-bit planes per operand: 2 (EGR_W_F16X2), 3 (EGR_W_BF16X3), 0 (fp32) */
+    int32_t tiles_m, tiles_n;    /* tiles per group */
+    int32_t grid_x, grid_y, grid_z, block;     /* the main launch */
+    int32_t split_k, ktiles_per_split;        /* K slices (1: none) of ktiles_per_split 32-deep chunks, none empty */
+    int32_t persistent;          /* workgroups walk several tiles (grid_x < tiles) */
+    int32_t cls_mode;            /* stride-2 data gradient as four output-parity classes (grid_y = 4) */
+    int32_t fused_reduce;        /* split_k > 1: the fused reduction was requested (egr_conv_set_splitk_fused) and the tiles fit a counter region */
+    int32_t reduce_pass;         /* split_k > 1: a reduction launch follows (also taken when fused_reduce finds no free counter region) */
+    int32_t bn_slabs;            /* egr_conv_aux.bn_partials: the slab count reported through bn_tiles_out (= tiles_m), else 0 */
+} egr_conv_plan_t;
+/* The plan of the launch the four entry points above would make for these arguments, without launching: same checks, same return
+ * code as the launch would give before its first kernel (EGR_E*, 0 = `out` is filled).  No data pointer is dereferenced (only
+ * NULL-ness and alignment count; `aux` is host memory and is read, nothing is written through aux->bn_tiles_out), no device is touched.
+ * mask = NULL: egr_conv2d_nhwc_ex_f32, else egr_conv2d_masked_ex_f32 (scale / shift / rowscale / rowmask NULL). */
+int egr_conv_plan(const egr_conv_desc* d, const float* x, const void* w, const float* scale, const float* shift,
+                  const float* res, const float* rowscale, const uint8_t* rowmask, const float* mask, const float* y,
+                  const float* workspace, size_t workspace_floats, const egr_conv_aux* aux, egr_conv_plan_t* out);
+
 /* Weight (and bias) gradient of the conv / linear layer described by `d` (forward geometry; d->groups same-shape problems
  * in one launch: x + g*gx, dy + g*gy, dw + g*gw, db + g*gp), the weight-side half of the training row: dw[co][(ci/32, kh, kw, ci%32)] (+)= sum over output pixels of dy[m][co] * im2col(x)[m][k],
  * db[co] (+)= sum_m dy[m][co] (db may be NULL).  dw is in the packed weight layout of egr_conv2d_nhwc_f32.  The pixels are
@@ -235,13 +276,15 @@ int egr_wgrad_last_kernel(void);
 /* Tuning knob for measurements: force the tile configuration of egr_conv2d_nhwc_f32
  * (-1 auto, 0 128x128, 1 256x64, 2 64x64, 3 128x32, 4 128x64).  Process-wide; results do not depend on it. */
 int egr_conv_force_config(int cfg);
-/* diagnostic (tests): the kernel the last egr_conv2d_nhwc_f32 / egr_conv2d_masked_f32 call launched - 0 fp32 MFMA,
- * 1 split-bf16 generic, 2 split-bf16 tap-sharing (3x3 / stride 1 / pad 1, tiles of whole image rows), 3 the stride-2 tap-sharing
- * kernel (3x3 / stride 2 / pad 1 on even images, taps shared by input parity class; env EGR_CONV_TAP2=0 turns it off), 4 the streaming 1x1 kernel (1x1 / stride 1, cin 64 / 128,
- * rows x groups >= 65536: weights stationary in LDS; env EGR_CONV_PW=0 turns it off), 5 the small fp32 1x1 kernel (1x1 / stride 1, fp32
- * weights, NHWC output, automatic split, K % 32 == 0 and K <= 1024, at most 256 tiles of 32 x 32 over all groups - any number when
- * K <= 64: one tile per workgroup, K split over its four waves, operands read straight from global memory; env EGR_CONV_SMALL=0 turns
- * it off; its sums differ from kernel 0's in the last bits (another fixed summation order).  egr_conv_set_tap(0) disables 2-4. */
+/* diagnostic (tests): the route (egr_conv_route) of the last plan that egr_conv2d_nhwc[_ex]_f32 / egr_conv2d_masked[_ex]_f32
+ * launched.  egr_conv_set_tap(0) disables routes 2-4 and 6.  The rules that pick a route are the plan_* functions of
+ * csrc/egr_conv.hip / egr_conv_tapx.hip, pinned case by case in tests/golden/conv_plan_cases.json.
+ * Environment (read once at load; all integers): EGR_CONV_TAP, EGR_CONV_TAP2, EGR_CONV_TAP64, EGR_CONV_PW, EGR_CONV_PW_MIN_ROWS,
+ * EGR_CONV_PW_BLOCKS, EGR_CONV_SMALL, EGR_CONV_SMALL_K, EGR_CONV_SMALL_TILES, EGR_CONV_SMALL_ROWS, EGR_CONV_PERSIST,
+ * EGR_CONV_PERSIST_KTILES, EGR_SPLITK_FUSED, EGR_SPLITK_MID_KT (automatic split-K of fp32 launches with 128 .. 511 workgroups: from
+ * this many 32-deep chunks, default 16, 0 = only from 64), EGR_SPLITK_TARGET (workgroups an automatic split aims at, default 1024),
+ * EGR_CONV_TAPX, EGR_CONV_TAPX_MIN_TILES, EGR_CONV_TAPX_BLOCKS, EGR_CONV_TAPX_PW, EGR_CONV_TAPX_TPW, EGR_CONV_TAPX_TRAIN,
+ * EGR_CONV_TAPX_FN - defaults and meanings: load_conv_knobs in csrc/egr_conv.hip. */
 int egr_conv_last_kernel(void);
 /* diagnostic / test knob: 1 = split-K launches run the reduction + epilogue in the last-arriving K slice of each tile (arrival
  * counters, agent-scope slab accesses) instead of a second kernel (splitk_reduce_kernel).  Both sum the slices in slice order.

@@ -26,7 +26,7 @@ for (n, hw, cin, cout, stride, res, label) in SHAPES:
     hip.lib.egr_conv_debug_stamps(C.c_void_p(buf.data_ptr()))
     run(); torch.cuda.synchronize()
     hip.lib.egr_conv_debug_stamps(None)
-    assert hip.lib.egr_conv_last_kernel() == 6, hip.lib.egr_conv_last_kernel()
+    assert hip.lib.egr_conv_last_kernel() == hip.ROUTE_TAPX, hip.lib.egr_conv_last_kernel()
     b = buf.view(256, 8, 8).double().cpu()
     m, l = b[:, :4].reshape(-1, 8), b[:, 4:].reshape(-1, 8)
     m, l = m[m[:, 3] > 0], l[l[:, 3] > 0]
