@@ -1102,6 +1102,34 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
     *reinterpret_cast<f32x4*>(v + idx * 4) = vv;
 }
 
+__global__ void set1_i32_kernel(int32_t* dst, int32_t v) { *dst = v; }
+
+// Gradient accumulation over a flat range (egr_grad_accum_f32): one streaming pass, 16 bytes per lane and access, grid-stride.
+// The mode is uniform over the launch (an argument, or one word of device memory).  The fp32 add is a single rounding, so
+// modes 0 / 1 are bit-reproducible; mode 2 squares and sums what it has just written in double: wave, block, one atomic per block.
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* acc, const float* g, int64_t n4, int32_t mode, const int32_t* mode_dev,
+                                                         double* sumsq) {
+    __shared__ double part[4];
+    if (mode_dev) mode = *mode_dev;
+    if (mode < 0 || mode > 2) return;
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(g + i * 4);
+        if (mode != 0) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(acc + i * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = a[e] + v[e];
+        }
+        *reinterpret_cast<f32x4*>(acc + i * 4) = v;
+        if (mode == 2) s += (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2] + (double)v[3] * v[3];
+    }
+    if (mode != 2) return;       // (uniform over the block: nobody is left waiting at the barrier below)
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(sumsq, (part[0] + part[1]) + (part[2] + part[3]));
+}
+
 // ------------------------------------------------------------------ multi-tensor re-packing
 __global__ __launch_bounds__(256) void repack_kernel(const egr_repack_desc* table, const int64_t* blocks) {
     const egr_repack_desc d = table[blocks[2 * blockIdx.x]];
@@ -1540,6 +1568,31 @@ extern "C" int egr_set4_f32(float* dst, float a, float b, float c, float d, void
     if (!dst) return EGR_ENULL;
     hipLaunchKernelGGL(set4_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dst, a, b, c, d);
     return egr_launch_status();
+}
+
+extern "C" int egr_set1_i32(int32_t* dst, int32_t value, void* stream) {
+    if (!dst) return EGR_ENULL;
+    hipLaunchKernelGGL(set1_i32_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dst, value);
+    return egr_launch_status();
+}
+
+static int grad_accum_launch(float* acc, const float* g, int64_t n, int32_t mode, const int32_t* mode_dev, double* sumsq, void* stream) {
+    if (n <= 0 || n % 4 != 0 || !aligned16(acc) || !aligned16(g)) return EGR_EINVAL;
+    int64_t blocks = (n / 4 + 255) / 256;
+    if (blocks > EGR_GRAD_ACCUM_MAX_BLOCKS) blocks = EGR_GRAD_ACCUM_MAX_BLOCKS;
+    hipLaunchKernelGGL(grad_accum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, acc, g, n / 4, mode, mode_dev, sumsq);
+    return egr_launch_status();
+}
+
+extern "C" int egr_grad_accum_f32(float* acc, const float* g, int64_t n, int32_t mode, double* sumsq, void* stream) {
+    if (!acc || !g || (mode == 2 && !sumsq)) return EGR_ENULL;
+    if (mode < 0 || mode > 2) return EGR_EINVAL;
+    return grad_accum_launch(acc, g, n, mode, nullptr, sumsq, stream);
+}
+
+extern "C" int egr_grad_accum_dev_f32(float* acc, const float* g, int64_t n, const int32_t* mode_dev, double* sumsq, void* stream) {
+    if (!acc || !g || !mode_dev || !sumsq) return EGR_ENULL;
+    return grad_accum_launch(acc, g, n, 0, mode_dev, sumsq, stream);
 }
 
 extern "C" int egr_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, float beta1,

@@ -20,6 +20,7 @@ TRAIN_EXPORTS = [
     "egr_upsample2x_bwd_f32", "egr_stem_wgrad_f32", "egr_planes_to_nhwc_f32", "egr_nhwc_to_planes_f32", "egr_stem_im2col_f32", "egr_layernorm_bwd_f32", "egr_joint_mha_bwd_f32",
     "egr_msda_gather_bwd_f32", "egr_colsum_f32", "egr_fold_rows_f32", "egr_jqa_sum_bwd_f32", "egr_rownorm_loss_f32",
     "egr_sumsq_f32", "egr_adamw_f32", "egr_adamw_dev_f32", "egr_set4_f32", "egr_bn_relu_maxpool_f32", "egr_bn_pool_backward_f32",
+    "egr_grad_accum_f32", "egr_grad_accum_dev_f32", "egr_set1_i32",
     "egr_repack_f32",   # the last one is bound in egorear_amd.repack
 ]
 
@@ -60,6 +61,9 @@ def _bind():
     lib.egr_adamw_f32.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp, f32, vp]
     lib.egr_set4_f32.argtypes = [vp, f32, f32, f32, f32, vp]
     lib.egr_adamw_dev_f32.argtypes = [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, vp, f32, vp]
+    lib.egr_grad_accum_f32.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.egr_grad_accum_dev_f32.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.egr_set1_i32.argtypes = [vp, i32, vp]
     lib.egr_bn_relu_maxpool_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.egr_bn_pool_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, vp, vp]
     for name in TRAIN_EXPORTS:
@@ -561,6 +565,33 @@ def set4(dst: torch.Tensor, a: float, b: float, c: float, d: float = 0.0):
     if dst.numel() < 4 or dst.dtype != torch.float32:
         raise RuntimeError("egorear_amd.train.set4: a 4-float device tensor expected")
     _launch("egr_set4_f32", lib.egr_set4_f32, _p(_dense(dst, "dst")), float(a), float(b), float(c), float(d), _stream())
+
+
+GRAD_ACCUM_MAX_BLOCKS = 2048      # EGR_GRAD_ACCUM_MAX_BLOCKS: blocks of 256 lanes x 4 floats; longer ranges go round the grid-stride loop
+
+
+def grad_accum(acc: torch.Tensor, g: torch.Tensor, mode, sumsq: Optional[torch.Tensor] = None):
+    """acc = g (mode 0), acc += g (1), acc += g and sumsq += sum acc^2 in double (2) over a flat range.  `mode` is an int, or a device
+    int32 tensor the kernel reads it from (one captured launch then serves every micro-batch; sumsq is required)."""
+    if acc.numel() != g.numel():
+        raise RuntimeError("egorear_amd.train.grad_accum: size mismatch")
+    if sumsq is not None and (sumsq.dtype != torch.float64 or sumsq.numel() != 1):
+        raise RuntimeError("egorear_amd.train.grad_accum: sumsq must be one float64")
+    _dense(acc, "acc"), _dense(g, "g")
+    if isinstance(mode, torch.Tensor):
+        if mode.dtype != torch.int32 or mode.numel() < 1 or sumsq is None:
+            raise RuntimeError("egorear_amd.train.grad_accum: a device mode is one int32, and needs sumsq")
+        _launch("egr_grad_accum_dev_f32", lib.egr_grad_accum_dev_f32, _p(acc), _p(g), acc.numel(), _p(mode, torch.int32),
+                _p(sumsq, torch.float64), _stream(), nbytes=12.0 * acc.numel())
+    else:
+        _launch("egr_grad_accum_f32", lib.egr_grad_accum_f32, _p(acc), _p(g), acc.numel(), int(mode), _p(sumsq, torch.float64), _stream(),
+                nbytes=(8.0 if int(mode) == 0 else 12.0) * acc.numel())
+
+
+def set1_i32(dst: torch.Tensor, value: int):
+    if dst.numel() < 1 or dst.dtype != torch.int32:
+        raise RuntimeError("egorear_amd.train.set1_i32: a device int32 tensor expected")
+    _launch("egr_set1_i32", lib.egr_set1_i32, _p(dst, torch.int32), int(value), _stream())
 
 
 from .hip import _guard_module  # noqa: E402  (a failed host-side check must not leave the launch-device record set)

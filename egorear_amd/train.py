@@ -1412,6 +1412,94 @@ def flat_layout(named, decay_all: bool = False):
     return order, slots, stage_range, off
 
 
+class StateMap:
+    """torch.optim.AdamW's parameter numbering for a module <-> the slots of the flat buffers.  entries: one
+    (index, group, name, shape, offset, numel) per parameter, sorted by index; groups: the `params` index lists of torch's
+    param_groups; decay[g]: whether group g is decayed; total: elements of a flat buffer."""
+    __slots__ = ("entries", "groups", "decay", "total")
+
+
+def optimizer_state_map(named_shapes, decay_all: bool = False) -> StateMap:
+    """Pure function of [(name, shape)] in named_parameters() order (no device, no tensors).  The numbering is the one the
+    reference's configure_optimizers produces: group 0 = the is_no_decay parameters (weight_decay 0.0), group 1 = the rest, each in
+    named_parameters() order, indices running 0.. across both (pose_3d_mvf_ex.py:219-234); decay_all: ONE group in parameters()
+    order (heatmap.py:151-154).  Offsets are flat_layout's."""
+    named = [(k, torch.Size(tuple(shape))) for k, shape in named_shapes]
+    _, slots, _, total = flat_layout(named, decay_all)
+    where = {k: (o, n) for k, o, n, _ in slots}
+    if decay_all:
+        buckets, decay = [[k for k, _ in named]], [True]
+    else:
+        buckets, decay = [[k for k, _ in named if is_no_decay(k)], [k for k, _ in named if not is_no_decay(k)]], [False, True]
+    shapes = dict(named)
+    sm = StateMap()
+    sm.entries, sm.groups, sm.decay, sm.total = [], [], decay, total
+    for g, names in enumerate(buckets):
+        first = len(sm.entries)
+        for k in names:
+            sm.entries.append((len(sm.entries), g, k, shapes[k], where[k][0], where[k][1]))
+        sm.groups.append(list(range(first, len(sm.entries))))
+    return sm
+
+
+def pack_optimizer_state(sm: StateMap, m: torch.Tensor, v: torch.Tensor, steps: int, lr_next: float, lr: float, betas, eps: float,
+                         weight_decay: float, extra: Optional[dict] = None) -> dict:
+    """Flat moment buffers -> a dict in the format of torch.optim.AdamW.state_dict() (the keys of a parameter group are those of the
+    installed torch's AdamW, so the dict loads into one), plus the top-level key "egorear_amd" for what torch has no slot for."""
+    # (a throw-away optimizer, only for the `defaults` of the installed torch: amsgrad, maximize, foreach, capturable, fused, ... -
+    # torch.optim.AdamW.step() indexes a loaded group by all of them)
+    stand_in = torch.optim.AdamW([torch.zeros(1)], lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    groups = []
+    for idx, decay in zip(sm.groups, sm.decay):
+        g = dict(stand_in.defaults)
+        g.update(lr=lr_next, betas=tuple(betas), eps=eps, weight_decay=weight_decay if decay else 0.0, params=list(idx))
+        groups.append(g)
+    state = {}
+    for i, _, _, shape, o, n in sm.entries:
+        state[i] = {"step": torch.tensor(float(steps)), "exp_avg": m[o:o + n].clone().view(shape),
+                    "exp_avg_sq": v[o:o + n].clone().view(shape)}
+    sd = {"state": state, "param_groups": groups}
+    if extra is not None:
+        sd["egorear_amd"] = extra
+    return sd
+
+
+def unpack_optimizer_state(sm: StateMap, sd: dict, m: torch.Tensor, v: torch.Tensor):
+    """The reverse: moments of a torch AdamW state_dict (ours, or one torch wrote for the same groups) into the flat buffers m, v
+    (zero where a parameter has no state: torch creates it lazily).  Unknown parameter-group keys are ignored.  Returns
+    (update count read from state[*]["step"], param_groups[0]["lr"]).  ValueError names the first parameter that does not fit."""
+    groups = sd["param_groups"]
+    if len(groups) != len(sm.groups):
+        raise ValueError(f"egorear_amd.train: optimizer state has {len(groups)} parameter groups, the module's optimizer {len(sm.groups)}")
+    index = {}
+    for g, (saved, mine) in enumerate(zip(groups, sm.groups)):
+        if len(saved["params"]) != len(mine):
+            ns = len(saved["params"])
+            k = sm.entries[mine[ns]][2] if ns < len(mine) else f"saved index {saved['params'][len(mine)]}"
+            raise ValueError(f"egorear_amd.train: parameter group {g} holds {ns} parameters, the module's {len(mine)} "
+                             f"(first without a partner: {k})")
+        index.update(zip(mine, saved["params"]))
+    state = sd.get("state", {})
+    fits = []
+    for i, _, k, shape, o, n in sm.entries:      # validate everything before anything is written
+        st = state.get(index[i])
+        if st is None or "exp_avg" not in st:
+            continue
+        for key in ("exp_avg", "exp_avg_sq"):
+            if tuple(st[key].shape) != tuple(shape):
+                raise ValueError(f"egorear_amd.train: {key} of parameter {index[i]} ({k}) has shape {tuple(st[key].shape)}, "
+                                 f"the parameter {tuple(shape)}")
+        fits.append((st, o, n))
+    m.zero_()
+    v.zero_()
+    steps = 0
+    for st, o, n in fits:
+        m[o:o + n].copy_(st["exp_avg"].reshape(-1))
+        v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+        steps = max(steps, int(round(float(st.get("step", 0)))))
+    return steps, float(groups[0]["lr"])
+
+
 class FusedAdamW:
     """AdamW over ONE flat fp32 buffer that the module's parameters are re-homed into (their .data become views), with
     flat gradient / moment buffers of the same layout: [no-decay parameters | decayed parameters].  A step is a gradient
@@ -1423,11 +1511,23 @@ class FusedAdamW:
     two parameter groups (pose_3d_mvf_ex.py:219-234) and its warm-up hook (:212-217).  The hook runs inside Lightning's
     `optimizer_step`, after `optimizer.step()` and BEFORE Lightning counts the step as completed, so during update t it sees
     `trainer.global_step == t - 1` and leaves lr * min(1, t / warmup_iters) behind for update t + 1: update 1 runs at the full
-    lr, update t >= 2 at lr * min(1, (t - 1) / warmup_iters) - update 2 at 1 / warmup_iters."""
+    lr, update t >= 2 at lr * min(1, (t - 1) / warmup_iters) - update 2 at 1 / warmup_iters.
+
+    accumulate = k > 1 (Lightning's accumulate_grad_batches): a second flat buffer `flat_acc` of the same layout collects the
+    gradients of k micro-batches (accumulate_grads: egr_grad_accum_f32, the mode read from device memory), and the update reads it
+    instead of flat_g.  `steps`, the warm-up and the bias corrections count UPDATES, like Lightning's global_step; `micro` counts
+    the micro-batches accumulated since the last update, `have_group` is the union of the tensors that received a gradient in any
+    of them.  With accumulate == 1 nothing of this exists and every launch is what it was.
+
+    state_dict / load_state_dict speak torch.optim.AdamW's own format (optimizer_state_map): a checkpoint the reference's optimizer
+    wrote resumes here, and the other way round."""
 
     def __init__(self, net: nn.Module, lr: float = 1e-3, weight_decay: float = 5e-4, clip: float = 5.0, warmup_iters: int = 500,
-                 betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, decay_all: bool = False):
+                 betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, decay_all: bool = False, accumulate: int = 1):
         self.net, self.lr, self.wd, self.clip, self.warmup, self.betas, self.eps = net, lr, weight_decay, clip, warmup_iters, betas, eps
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"egorear_amd.train: accumulate must be a positive integer, got {accumulate!r}")
+        self.accumulate, self.decay_all = int(accumulate), decay_all
         self.pg = process_group
         self.force_collective = False        # issue the stage all-reduces for a one-rank group too (RCCL rehearsal on one GPU)
         named = list(net.named_parameters())
@@ -1451,6 +1551,13 @@ class FusedAdamW:
         self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)        # {lr, 1 - b1^t, sqrt(1 - b2^t)} of the coming update
         self.steps = 0
         self.lr_scale_epoch = 1.0            # MultiStepLR(lr_decay_epochs, 0.1) factor, set by the caller per epoch
+        self.state_map = optimizer_state_map([(k, p.shape) for k, p in named], decay_all)
+        # gradient accumulation: the second flat buffer exists only when asked for (504 MB for the full model)
+        self.flat_acc = torch.zeros(off, device=dev, dtype=torch.float32) if self.accumulate > 1 else None
+        self.mode_dev = torch.zeros(1, dtype=torch.int32, device=dev) if self.accumulate > 1 else None
+        self.micro = 0                       # micro-batches accumulated since the last update
+        self.have_group = set()              # names that received a gradient in any of them
+        self.fused_sumsq = False             # the accumulation launches of the group's last micro-batch left sum acc^2 in self.sumsq
 
     def lr_at(self, t: int) -> float:
         return self.lr * self.lr_scale_epoch * (1.0 if t <= 1 else min(1.0, float(t - 1) / float(self.warmup)))
@@ -1469,12 +1576,14 @@ class FusedAdamW:
                 runs.append(cur)
         return runs
 
-    def reduce_stage(self, stage: int):
+    def reduce_stage(self, stage: int, buf: Optional[torch.Tensor] = None):
         """Start the gradient all-reduce of one finished stage (SUM; the 1/world of DDP's average is in the loss seed).
-        It runs on the communication stream of the process group while the reverse pass continues."""
+        It runs on the communication stream of the process group while the reverse pass continues.  buf: the flat buffer whose
+        stage range is reduced - flat_g, or flat_acc for an accumulated group (once per update)."""
         from .dist import allreduce_gradients_
         b, e = self.stage_range[stage]
-        h = allreduce_gradients_(self.flat_g[b:e], self.pg, async_op=True, force=self.force_collective)
+        src = self.flat_g if buf is None else buf
+        h = allreduce_gradients_(src[b:e], self.pg, async_op=True, force=self.force_collective)
         if h is not None:
             self.pending.append(h)
 
@@ -1487,15 +1596,107 @@ class FusedAdamW:
         T.set4(self.hyper, self.lr_at(t), 1.0 - self.betas[0] ** t, math.sqrt(1.0 - self.betas[1] ** t))
 
     def enqueue_update(self, have) -> None:
-        """sumsq + clip + AdamW launches for the names whose gradient views were written (every stage already reduced)."""
+        """sumsq + clip + AdamW launches for the names whose gradient views were written (every stage already reduced).  Accumulating:
+        from flat_acc, and without the sum-of-squares pass when the last micro-batch's accumulation launches carried it."""
         for h in self.pending:
             h.wait()
         self.pending = []
         runs = self._runs(have)
-        T.sumsq(self.flat_g, self.sumsq)       # one pass over the whole flat buffer: slots that never receive a gradient stay zero
+        src = self.flat_acc if self.flat_acc is not None else self.flat_g
+        if not (self.flat_acc is not None and self.fused_sumsq):
+            T.sumsq(src, self.sumsq)           # one pass over the whole flat buffer: slots that never receive a gradient stay zero
         for o, n, decay in runs:
-            T.adamw_dev(self.flat_p[o:o + n], self.flat_g[o:o + n], self.m[o:o + n], self.v[o:o + n], self.hyper, self.betas[0], self.betas[1],
+            T.adamw_dev(self.flat_p[o:o + n], src[o:o + n], self.m[o:o + n], self.v[o:o + n], self.hyper, self.betas[0], self.betas[1],
                         self.eps, self.wd if decay else 0.0, self.sumsq, self.clip)
+
+    # ---- gradient accumulation
+    def begin_micro(self, fuse_sumsq: bool) -> bool:
+        """In front of a micro-batch's forward: put the mode its accumulation launches will read into device memory (by kernel
+        argument, like the update's scalars).  0 = first of the group (flat_acc = flat_g, no clearing), 1 = add, 2 = add + sum of
+        squares on the group's last one - unless fuse_sumsq is off (multi-process: the norm is that of the REDUCED sum, taken by
+        the update).  Returns whether this micro-batch completes the group."""
+        last = self.micro + 1 >= self.accumulate
+        self.fused_sumsq = bool(fuse_sumsq and last and self.micro > 0)
+        T.set1_i32(self.mode_dev, 0 if self.micro == 0 else (2 if self.fused_sumsq else 1))
+        return last
+
+    def accumulate_grads(self, stage: Optional[int] = None):
+        """flat_acc (=, +=) flat_g over one finished gradient stage's range, or over the whole buffer.  Slots that receive no
+        gradient hold zeros in both.  self.sumsq must have been cleared in front of the first launch of a micro-batch."""
+        b, e = (0, self.total) if stage is None else self.stage_range.get(stage, (0, 0))
+        if e > b:
+            T.grad_accum(self.flat_acc[b:e], self.flat_g[b:e], self.mode_dev, self.sumsq)
+
+    def end_micro(self, have):
+        self.micro += 1
+        self.have_group |= set(have)
+
+    def end_group(self):
+        self.micro, self.have_group, self.fused_sumsq = 0, set(), False
+
+    # ---- state in torch.optim.AdamW's format
+    def state_dict(self) -> dict:
+        """What torch.optim.AdamW.state_dict() holds for the optimizer the reference's configure_optimizers builds over this module
+        (optimizer_state_map: groups, numbering), moments as clones shaped like their parameters; the groups' lr is the value the
+        reference's warm-up hook leaves behind for the NEXT update, lr_at(steps + 1).  Every parameter carries state (moments of a
+        tensor that never received a gradient are zero).  Key "egorear_amd": steps, lr_scale_epoch, accumulate, the micro-batch
+        counter and - inside a half-done group - flat_acc and the names accumulated so far (single-process runs only: with several
+        ranks flat_acc is a per-rank partial sum and a half-done group is refused, RuntimeError)."""
+        extra = {"steps": self.steps, "lr_scale_epoch": self.lr_scale_epoch, "accumulate": self.accumulate, "micro": self.micro}
+        if self.micro > 0:
+            self._refuse_partial_sum_across_ranks("saved")
+            extra["flat_acc"], extra["have_group"] = self.flat_acc.clone(), sorted(self.have_group)
+        return pack_optimizer_state(self.state_map, self.m, self.v, self.steps, self.lr_at(self.steps + 1), self.lr, self.betas, self.eps,
+                                    self.wd, extra)
+
+    def _refuse_partial_sum_across_ranks(self, verb: str):
+        """Inside a group flat_acc is THIS rank's unreduced sum (no collective before the group's last micro-batch).  Lightning saves
+        from rank 0 only, so a resume would hand rank 0's partial sum to every rank: a half-done group travels through a checkpoint
+        in single-process runs only."""
+        from .dist import world_size
+        if world_size(self.pg) > 1:
+            raise RuntimeError(f"egorear_amd.train: a half-done accumulation group ({self.micro or 'some'} micro-batches pending) cannot be "
+                               f"{verb} with a process group of {world_size(self.pg)} ranks - flat_acc is a per-rank partial sum; finish "
+                               "the group or call flush() on every rank first")
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Accepts state_dict()'s dict and a plain torch AdamW state_dict with the same groups (`optimizer_states[0]` of a checkpoint
+        the reference wrote).  Without the "egorear_amd" key the update count comes from state[*]["step"] and lr_scale_epoch from
+        param_groups[0]["lr"] against the warm-up rule.  ValueError (nothing written) on a wrong parameter count or shape."""
+        extra = sd.get("egorear_amd")
+        if extra is not None and extra.get("micro", 0) > 0:
+            if extra.get("accumulate") != self.accumulate or self.flat_acc is None:
+                raise ValueError(f"egorear_amd.train: the state was saved inside a group of accumulate={extra.get('accumulate')}, "
+                                 f"this optimizer runs accumulate={self.accumulate}")
+            self._refuse_partial_sum_across_ranks("loaded")
+            if tuple(extra["flat_acc"].shape) != tuple(self.flat_acc.shape):
+                raise ValueError(f"egorear_amd.train: flat_acc holds {extra['flat_acc'].numel()} elements, the module's layout {self.total}")
+        steps, lr0 = unpack_optimizer_state(self.state_map, sd, self.m, self.v)
+        self.end_group()
+        if extra is not None:
+            self.steps, self.lr_scale_epoch = int(extra["steps"]), float(extra["lr_scale_epoch"])
+            if extra.get("micro", 0) > 0:
+                self.flat_acc.copy_(extra["flat_acc"])
+                self.micro, self.have_group = int(extra["micro"]), set(extra["have_group"])
+        else:
+            self.steps, self.lr_scale_epoch = steps, 1.0
+            self.lr_scale_epoch = lr0 / self.lr_at(steps + 1)
+        self.pending = []
+
+    def rehome(self) -> int:
+        """Parameters of the module that are not (or no longer) their view into flat_p - a load that REPLACED tensors or Parameter
+        objects, e.g. load_state_dict(assign=True): their values are copied into the slot and .data is pointed at it.  Returns how
+        many had moved."""
+        moved = 0
+        cur = dict(self.net.named_parameters())
+        with torch.no_grad():
+            for k, o, n, _ in self.slots:
+                p, home = cur[k], self.flat_p[o:o + n]
+                if p.data_ptr() != home.data_ptr():
+                    home.copy_(p.detach().reshape(-1))
+                    p.data = home.view(p.shape)
+                    moved += 1
+        return moved
 
     def step(self, have) -> None:
         """`have`: names whose gradient views were written this step.  Every stage must have been reduced (reduce_stage)."""
@@ -1516,12 +1717,15 @@ class Trainer:
     as its gradients are complete and overlaps with the replay of the stages that follow."""
 
     def __init__(self, net: nn.Module, lr: float = 1e-3, weight_decay: float = 5e-4, clip: float = 5.0, warmup_iters: int = 500,
-                 w_mpjpe: float = W_MPJPE, w_heatmap: float = W_HEATMAP, process_group=None, use_graph: bool = False):
+                 w_mpjpe: float = W_MPJPE, w_heatmap: float = W_HEATMAP, process_group=None, use_graph: bool = False,
+                 accumulate: int = 1):
         self.net = net
-        self.opt = FusedAdamW(net, lr, weight_decay, clip, warmup_iters, process_group=process_group)
+        self.opt = FusedAdamW(net, lr, weight_decay, clip, warmup_iters, process_group=process_group, accumulate=accumulate)
         self.w_mpjpe, self.w_heatmap = w_mpjpe, w_heatmap
         self.use_graph = use_graph
         self.graph = None
+        self._tail = None           # accumulate > 1: the captured update (clip + AdamW from flat_acc), replayed behind a group's last micro-batch
+        self._last = False          # accumulate > 1: the micro-batch being run completes its group
         self._eager_done = 0
         self._static = None
         self._graph_out = None
@@ -1541,18 +1745,44 @@ class Trainer:
         S = Step(net, img.device)
         S.gviews = self.opt.gviews
         from .dist import grad_seed_scale
-        if hook is not None:
-            S.stage_hook = hook                    # capture: cuts the recording at every stage boundary
-        elif self._distributed():
-            S.stage_hook = self.opt.reduce_stage   # bucketed all-reduce overlapped with the rest of the reverse pass
+        self._set_stage_hook(S, hook)
         with torch.no_grad():
             preds, hms, aux = forward_train(S, net, img, ctm)
-            loss_and_seed(S, preds, hms, gt_pose, gt_heatmap, self.w_mpjpe, self.w_heatmap, grad_scale=grad_seed_scale(self.opt.pg))
+            loss_and_seed(S, preds, hms, gt_pose, gt_heatmap, self.w_mpjpe, self.w_heatmap,
+                          grad_scale=grad_seed_scale(self.opt.pg) / self.opt.accumulate)
+            self._close(S, update)
+        return S, (preds, hms, aux)
+
+    def _set_stage_hook(self, S: Step, hook):
+        opt = self.opt
+        if hook is not None:
+            S.stage_hook = hook                    # capture: cuts the recording at every stage boundary
+        elif self._distributed() and opt.accumulate == 1:
+            S.stage_hook = opt.reduce_stage        # bucketed all-reduce overlapped with the rest of the reverse pass
+        elif self._distributed():
+            # accumulating: every finished stage is added to its range of flat_acc; no collective before the group's last micro-batch
+            # (DDP's no_sync), where the range goes to the all-reduce as soon as it is complete - the overlap of the plain step
+            def stage_done(stage):
+                opt.accumulate_grads(stage)
+                if self._last and stage in opt.stage_range:
+                    opt.reduce_stage(stage, opt.flat_acc)
+            S.stage_hook = stage_done
+
+    def _close(self, S: Step, update: bool):
+        """Behind the loss seeds: the reverse pass, then clip + AdamW - or, accumulating, this micro-batch added to flat_acc (one
+        process: ONE pass over the whole buffer behind the reverse pass, which keeps the two-stream schedule a stage hook would
+        switch off; several: per stage, in the hook).  The group's update is the caller's (Trainer._update_group)."""
+        opt = self.opt
+        if opt.accumulate == 1:
             _finish_backward(S)
             if update:
-                self.opt.begin_update()
-            self.opt.enqueue_update(S.pgrads.keys())
-        return S, (preds, hms, aux)
+                opt.begin_update()
+            opt.enqueue_update(S.pgrads.keys())
+            return
+        opt.sumsq.zero_()             # (mode 2 adds to it; in front of the reverse pass, whose stage hooks accumulate)
+        _finish_backward(S)
+        if S.stage_hook is None:
+            opt.accumulate_grads()
 
     def _invalidate(self):
         from .engine import invalidate
@@ -1581,6 +1811,8 @@ class Trainer:
 
     def step(self, img, ctm, gt_pose, gt_heatmap):
         """Returns (loss terms (6,) float64 device tensor, outputs).  Parameters are updated in place."""
+        if self.opt.accumulate > 1:
+            return self._micro_step(img, ctm, gt_pose, gt_heatmap)
         from .dist import world_size
         self.sync_buffers(force=self.opt.force_collective)   # eager, in front of the (possibly replayed) forward
         if self.graph is not None:
@@ -1617,6 +1849,122 @@ class Trainer:
         self._eager_done += 1
         self._invalidate()
         return S.loss_terms, outs
+
+    # ---- gradient accumulation (accumulate > 1): `step` is called once per micro-batch
+    def pending_micro_steps(self) -> int:
+        """Micro-batches accumulated since the last optimizer update."""
+        return self.opt.micro
+
+    def flush(self) -> bool:
+        """Update NOW from what has been accumulated (an epoch's short tail of r < accumulate micro-batches); False when nothing is
+        pending.  The sum keeps the seed scale it was accumulated under, 1 / accumulate: Lightning does the same at the end of an
+        epoch (it divides every micro-batch's loss by accumulate_grad_batches and steps on the last batch whatever the count), so a
+        tail of r micro-batches takes a step from r / accumulate of a full group's average, not from the average of the r.
+        With a process group the micro-batches so far issued no collective, so every stage's range of flat_acc is all-reduced here,
+        in front of the update (DDP synchronises on an epoch's last batch too): every rank must call flush() with the same number
+        of micro-batches pending, as equal-length data shards guarantee."""
+        opt = self.opt
+        if opt.micro == 0:
+            return False
+        opt.fused_sumsq = False          # the norm of a part-group (and, across ranks, of the reduced) sum: the update's own pass over flat_acc
+        if self._distributed():
+            for stage in sorted(opt.stage_range):
+                opt.reduce_stage(stage, opt.flat_acc)
+        self._update_group()
+        return True
+
+    def _update_group(self, tail=None):
+        """clip + AdamW from flat_acc (every stage reduced), eagerly or as the captured tail; the weights changed: packs are dropped."""
+        opt = self.opt
+        opt.begin_update()
+        if tail is not None:
+            tail.replay()
+        else:
+            with torch.no_grad():
+                opt.enqueue_update(opt.have_group)
+        opt.end_group()
+        self._invalidate()
+
+    def _micro_step(self, img, ctm, gt_pose, gt_heatmap):
+        """One micro-batch of a group of `accumulate`: forward + backward + accumulation; the group's last one also runs clip + AdamW.
+        k accumulated micro-batches are a k-rank data-parallel step: BatchNorm statistics per micro-batch (running statistics and
+        num_batches_tracked advance every time), the loss seed scaled by 1 / k on top of 1 / world, ONE clip and ONE AdamW on the
+        sum.  In between no sum of squares, no update, no collective, and the packed inference weights stay valid (nothing changed).
+        use_graph: two captures per input shape - the micro-batch body, which reads its accumulation mode from device memory, and
+        the update tail; nothing is captured again per micro-batch."""
+        opt = self.opt
+        dist_ = self._distributed()
+        if self.use_graph and dist_:
+            raise NotImplementedError("egorear_amd.train: use_graph with a process group and accumulate > 1 is not built (the segmented "
+                                      "capture would need a no-collective and a collective replay schedule); run it eagerly or with accumulate=1")
+        self.sync_buffers(force=opt.force_collective)
+        args = (img, ctm, gt_pose, gt_heatmap)
+        if self.graph is not None and all((a is None) == (b is None) and (a is None or a.shape == b.shape) for a, b in zip(self._static, args)):
+            for dst, src in zip(self._static, args):
+                if dst is not None:
+                    dst.copy_(src, non_blocking=True)
+            last = opt.begin_micro(fuse_sumsq=True)
+            self.graph.replay()
+            opt.end_micro(self._graph_step.pgrads.keys())
+            if last:
+                self._update_group(self._tail)
+            return self._graph_out
+        if self.use_graph and self.graph is None and self._eager_done >= 2:
+            try:
+                self._capture_micro(*args)
+            except Exception as exc:      # capture is an optimisation: any refusal leaves the eager path in charge - loudly
+                import warnings
+                warnings.warn(f"egorear_amd.train: hipGraph capture of the micro-step failed ({type(exc).__name__}: {exc}); continuing eagerly")
+                self.graph, self._tail, self.use_graph = None, None, False
+                torch.cuda.synchronize()
+            else:
+                return self._micro_step(*args)
+        self._last = opt.begin_micro(fuse_sumsq=not dist_)
+        S, outs = self._run(*args, update=False)
+        opt.end_micro(S.pgrads.keys())
+        self._eager_done += 1
+        if self._last:
+            self._update_group()
+        self._last = False
+        return S.loss_terms, outs
+
+    def _capture_micro(self, img, ctm, gt_pose, gt_heatmap):
+        dev = img.device
+        self._static = [None if t is None else t.detach().to(device=dev, dtype=torch.float32).clone().contiguous()
+                        for t in (img, ctm, gt_pose, gt_heatmap)]
+        torch.cuda.synchronize()
+        body = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(body, capture_error_mode="relaxed"):
+            S, outs = self._run(*self._static, update=False)           # recorded, not executed: nothing is counted
+        tail = torch.cuda.CUDAGraph()
+        saved, self.opt.fused_sumsq = self.opt.fused_sumsq, True       # a replayed group always ends in a mode-2 micro-batch
+        try:
+            with torch.cuda.graph(tail, capture_error_mode="relaxed"), torch.no_grad():
+                self.opt.enqueue_update(set(self.opt.have_group) | set(S.pgrads.keys()))
+        finally:
+            self.opt.fused_sumsq = saved
+        self.graph, self._tail, self._graph_step, self._graph_out = body, tail, S, (S.loss_terms, outs)
+
+    # ---- checkpoint / resume
+    def state_dict(self) -> dict:
+        """{"optimizer": FusedAdamW.state_dict() (torch.optim.AdamW's format), "lr_scale_epoch": ...}.  Model weights and BatchNorm
+        buffers stay with net.state_dict().  With several ranks, checkpoint between groups (pending_micro_steps() == 0, e.g. after
+        flush() at an epoch's end): a half-done group is a per-rank partial sum and is refused."""
+        return {"optimizer": self.opt.state_dict(), "lr_scale_epoch": self.opt.lr_scale_epoch}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore state_dict()'s dict ("optimizer" may be a plain torch AdamW state_dict).  Call it AFTER net.load_state_dict: the
+        parameters are checked to still be views into the flat buffer and re-homed if the load replaced their tensors; captured
+        graphs and packed weights are dropped, the next steps run eagerly and capture again.  "lr_scale_epoch" absent or None keeps
+        what the optimizer's own load found (the extra key, or param_groups[0]["lr"] of a plain torch dict against the warm-up rule)."""
+        self.opt.load_state_dict(sd["optimizer"])
+        if sd.get("lr_scale_epoch") is not None:
+            self.opt.lr_scale_epoch = float(sd["lr_scale_epoch"])
+        self.opt.rehome()
+        self.net.__dict__.pop("_egr_pack_cache", None)     # (its tables hold the tensors of before the load; no graph points into it any more)
+        self.graph = self._tail = self._static = self._graph_out = self._graph_step = self._cuts = None
+        self._eager_done = 0
+        self._invalidate()
 
     def _capture(self, img, ctm, gt_pose, gt_heatmap):
         dev = img.device
@@ -1669,7 +2017,7 @@ class HeatmapTrainer(Trainer):
     Trainer's."""
 
     def __init__(self, net: nn.Module, lr: float = 1e-3, weight_decay: float = 5e-3, clip: float = 5.0, warmup_iters: int = 500,
-                 w_heatmap: float = 10.0, process_group=None, use_graph: bool = False):
+                 w_heatmap: float = 10.0, process_group=None, use_graph: bool = False, accumulate: int = 1):
         from .estimator import EgoPoseFormerHeatmap, EgoPoseFormerHeatmapMVFEX
         if isinstance(net, EgoPoseFormerHeatmapMVFEX):
             self.kind = "mvfex"
@@ -1678,12 +2026,13 @@ class HeatmapTrainer(Trainer):
         else:
             raise RuntimeError("egorear_amd.train.HeatmapTrainer: EgoPoseFormerHeatmap or EgoPoseFormerHeatmapMVFEX expected")
         self.net = net
-        self.opt = FusedAdamW(net, lr, weight_decay, clip, warmup_iters, process_group=process_group, decay_all=True)
+        self.opt = FusedAdamW(net, lr, weight_decay, clip, warmup_iters, process_group=process_group, decay_all=True, accumulate=accumulate)
         self.w_mpjpe, self.w_heatmap = 0.0, w_heatmap
         self.use_graph = use_graph
         self.graph = None
         self._eager_done = 0
-        self._static = self._graph_out = self._graph_step = self._cuts = None
+        self._static = self._graph_out = self._graph_step = self._cuts = self._tail = None
+        self._last = False
         from .dist import BufferSync, world_size
         self.buffers = BufferSync(net, process_group) if world_size(process_group) > 1 else None
 
@@ -1692,11 +2041,8 @@ class HeatmapTrainer(Trainer):
         S = Step(net, img.device)
         S.gviews = self.opt.gviews
         from .dist import grad_seed_scale
-        if hook is not None:
-            S.stage_hook = hook
-        elif self._distributed():
-            S.stage_hook = self.opt.reduce_stage
-        scale = grad_seed_scale(self.opt.pg)
+        self._set_stage_hook(S, hook)
+        scale = grad_seed_scale(self.opt.pg) / self.opt.accumulate
         with torch.no_grad():
             if self.kind == "heatmap":
                 hms = [heatmap_forward_train(S, net, img)]
@@ -1711,10 +2057,7 @@ class HeatmapTrainer(Trainer):
                 g = gt if gt.shape[1] == V else gt[:, :V].contiguous()
                 S.G.add(h, T.mse_loss(h, g, self.w_heatmap * V * scale, terms[i:i + 1]))
             S.loss_terms = terms if scale == 1.0 else terms / scale
-            _finish_backward(S)
-            if update:
-                self.opt.begin_update()
-            self.opt.enqueue_update(S.pgrads.keys())
+            self._close(S, update)
         return S, outs
 
     def _invalidate(self):

@@ -173,6 +173,21 @@ int egr_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, c
                       float eps, float weight_decay, const double* grad_sumsq, float clip, void* stream);
 int egr_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int32_t step, const double* grad_sumsq, float clip, void* stream);
+/* Gradient accumulation (Lightning's accumulate_grad_batches): one streaming pass over a flat range that follows the slot rules of
+ * the flat buffers (n % 4 == 0, both pointers 16-byte aligned; EGR_EINVAL otherwise).
+ *   mode 0: acc = g            (first micro-batch of a group: acc needs no clearing)
+ *   mode 1: acc = acc + g      (one fp32 rounding per element: modes 0 / 1 are bit-reproducible)
+ *   mode 2: acc = acc + g and *sumsq += sum acc^2 of the values just written, squares and sums in double (block partials, one
+ *           double add per block, like egr_sumsq_f32): the updating micro-batch needs no separate sum-of-squares read.
+ * The mode from device memory is a SECOND entry, egr_grad_accum_dev_f32 (*mode_dev is read by the kernel; sumsq must be given
+ * because the mode is not known on the host), in the way egr_adamw_dev_f32 sits next to egr_adamw_f32: one captured hipGraph
+ * then serves the first, the middle and the last micro-batch.  A device value outside 0..2 makes the launch a no-op.
+ * egr_set1_i32 writes that word from a kernel argument (same reason as egr_set4_f32).
+ * The launch is capped at EGR_GRAD_ACCUM_MAX_BLOCKS blocks of 256 lanes x 4 floats; longer ranges go round the grid-stride loop. */
+#define EGR_GRAD_ACCUM_MAX_BLOCKS 2048
+int egr_grad_accum_f32(float* acc, const float* g, int64_t n, int32_t mode, double* sumsq, void* stream);
+int egr_grad_accum_dev_f32(float* acc, const float* g, int64_t n, const int32_t* mode_dev, double* sumsq, void* stream);
+int egr_set1_i32(int32_t* dst, int32_t value, void* stream);
 
 /* ---- parameter re-packing, all tensors of a step in ONE launch.  Every optimisation step the kernels' weight layouts
  * (forward operand [cout_pad][cin_pad/32][taps][32], data-gradient operand [cin_pad32][cout_pad/32][taps][32], padded bias

@@ -1,10 +1,12 @@
 """Training-step timing and per-kernel breakdown (config 5: ego4view_rw_pose3d, batch 32 per GPU).
 
     python tools/train_bench.py [--batch 32] [--steps 5]
+    python tools/train_bench.py --graph --accumulate 8      # gradient accumulation: ms per micro-step and per optimizer update
 """
 import argparse
 import collections
 import copy
+import json
 import os
 import sys
 import time
@@ -24,17 +26,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="replay the step as one hipGraph")
     ap.add_argument("--dump", default="", help="write every launch of the instrumented step (order, us, name, tag) to this file")
+    ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer update (--steps / --warmup then count updates)")
+    ap.add_argument("--json", default="", help="with --accumulate: also write the figures to this file")
     a = ap.parse_args()
     dev = "cuda:0"
     net = EgoPoseFormerMVFEX(**copy.deepcopy(configs.pose3d_cfg("ego4view_rw")))
     synth.load_synth(net, 42)
     net = net.to(dev)
-    tr = train.Trainer(net, use_graph=a.graph)
+    tr = train.Trainer(net, use_graph=a.graph, accumulate=a.accumulate)
     B = a.batch
     img = synth.synth_images(B, 4, seed=1234).to(dev)
     ctm = synth.synth_coord_trans_mat(B).to(dev)
     gt_pose = synth.synth_gt_pose(B).to(dev)
     gt_hm = generate_target(synth.synth_joint_px(B).to(dev)).contiguous()
+    if a.accumulate > 1:
+        return accumulate_leg(a, tr, (img, ctm, gt_pose, gt_hm))
     for _ in range(a.warmup):
         terms, _ = tr.step(img, ctm, gt_pose, gt_hm)
     torch.cuda.synchronize()
@@ -87,6 +93,39 @@ def main():
             cur[2] += fl
     for (name, tag), (ms, n, fl) in sorted(by_tag.items(), key=lambda kv: -kv[1][0])[:60]:
         print(f"    {ms:7.3f} ms x{n:3d} {fl / ms / 1e9 if ms > 0 else 0:7.1f} TF  {name:14s} {tag}")
+
+
+def accumulate_leg(a, tr, args):
+    """Device time per micro-step (event pairs on the step's stream), split into the ones that only accumulate and the one that
+    also clips and updates, and the wall time per optimizer update."""
+    K = a.accumulate
+    for _ in range(a.warmup * K):
+        tr.step(*args)
+    assert tr.pending_micro_steps() == 0
+    torch.cuda.synchronize()
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps * K + 1)]
+    t0 = time.perf_counter()
+    marks[0].record()
+    for i in range(a.steps * K):
+        terms, _ = tr.step(*args)
+        marks[i + 1].record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / a.steps
+    ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps * K)]
+    plain = [t for i, t in enumerate(ms) if (i + 1) % K]
+    upd = [t for i, t in enumerate(ms) if (i + 1) % K == 0]
+    res = {"batch": a.batch, "accumulate": K, "graph": bool(a.graph and tr.graph is not None), "updates_timed": a.steps,
+           "ms_micro_step_accumulating": sum(plain) / len(plain), "ms_micro_step_updating": sum(upd) / len(upd),
+           "ms_per_optimizer_update": wall * 1e3, "optimizer_updates": tr.opt.steps, "loss": float(terms.sum()),
+           "mem_gib": torch.cuda.max_memory_allocated() / 2**30}
+    print(f"batch {a.batch} x accumulate {K}: {res['ms_micro_step_accumulating']:.2f} ms per accumulating micro-step, "
+          f"{res['ms_micro_step_updating']:.2f} ms per updating micro-step, {res['ms_per_optimizer_update']:.2f} ms per optimizer update "
+          f"({a.batch * K / wall:.1f} frames/s), mem {res['mem_gib']:.1f} GiB")
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
