@@ -86,9 +86,13 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 //            2^e chosen per launch from their recorded abs-max (amax_in), the weights per output channel at pack time; the
 //            accumulators are multiplied by the inverse before the epilogue.  Half the matrix instructions and two thirds of
 //            the operand bytes of the bf16 scheme.
-constexpr int split_npr(int npl) { return npl == 3 ? 6 : 3; }
+//   NPL = 1 (EGR_W_F16X2 | EGR_W_F16X1, role-split kernel only): x 2^e = h alone, fp16-rounded operands, ONE product - the opt-in
+//            fast policy; the weight operand is the h plane of the two-plane image
+constexpr int split_npr(int npl) { return npl == 3 ? 6 : (npl == 2 ? 3 : 1); }
 // plane of the A operand whose last use is product t (-1: none): its registers can be refilled for the next tap behind it
-constexpr int split_free_a(int npl, int t) { return npl == 3 ? (t == 0 ? 2 : (t == 3 ? 1 : (t == 5 ? 0 : -1))) : (t == 0 ? 1 : (t == 2 ? 0 : -1)); }
+constexpr int split_free_a(int npl, int t) {
+    return npl == 3 ? (t == 0 ? 2 : (t == 3 ? 1 : (t == 5 ? 0 : -1))) : (npl == 2 ? (t == 0 ? 1 : (t == 2 ? 0 : -1)) : (t == 0 ? 0 : -1));
+}
 
 template <int NPL>
 __device__ __forceinline__ f32x16 mfma_split(const u32x4& a, const u32x4& b, const f32x16& c) {
@@ -126,6 +130,16 @@ __device__ __forceinline__ void split4_f16(float v0, float v1, float v2, float v
         "v_fma_mixhi_f16 %1, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
         "v_fma_mixhi_f16 %3, %7, %8, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
         : "=&v"(h01), "=&v"(l01), "=&v"(h23), "=&v"(l23)
+        : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(s));
+}
+
+// the high planes alone (one-product launches): four values * s -> two packed fp16 pairs, round to nearest even
+__device__ __forceinline__ void cvt4_f16(float v0, float v1, float v2, float v3, float s, unsigned& h01, unsigned& h23) {
+    asm("v_fma_mixlo_f16 %0, %2, %6, 0\n\t"
+        "v_fma_mixlo_f16 %1, %4, %6, 0\n\t"
+        "v_fma_mixhi_f16 %0, %3, %6, 0\n\t"
+        "v_fma_mixhi_f16 %1, %5, %6, 0"
+        : "=&v"(h01), "=&v"(h23)
         : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(s));
 }
 
@@ -196,6 +210,7 @@ struct ConvProblem {
     size_t workspace_floats;
     bool workspace_aligned;      // a.ws is 16-byte aligned
     bool x6, h2;                 // split kernels (bf16 x 3 / fp16 x 2); h2: the fp16 scheme
+    bool h1;                     // EGR_W_F16X1 came with EGR_W_F16X2 (a.d.w_format holds the plain format): one product where a kernel has that form
 };
 
 // A route has fixed its tile: the fields every route fills the same way (one workgroup per tile until the route says otherwise).
@@ -203,7 +218,7 @@ inline egr_conv_plan_t plan_tile(const ConvProblem& p, int route, int bm, int bn
     const ConvArgs& a = p.a;
     egr_conv_plan_t pl = {};
     pl.route = route; pl.bm = bm; pl.bn = bn; pl.variant = variant;
-    pl.planes = p.h2 ? 2 : (p.x6 ? 3 : 0);
+    pl.planes = p.h2 ? 2 : (p.x6 ? 3 : 0);                   // (plan_tapx: 1 for its one-product variants)
     pl.tiles_m = (a.M + bm - 1) / bm;
     pl.tiles_n = (a.Npad + bn - 1) / bn;
     pl.grid_x = pl.tiles_m * pl.tiles_n; pl.grid_y = 1; pl.grid_z = a.d.groups;

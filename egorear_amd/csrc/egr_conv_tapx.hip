@@ -65,12 +65,18 @@ constexpr int tapx_hp(int bm, int stride) { return stride == 2 ? 4 * tapx_cls(bm
 // sum / sum of squares (double) and extremes in a slab (egr_conv_aux.bn_partials, the layout of conv_igemm's epilogue: one slab per
 // M tile); 2 = data gradient behind a ReLU: dx = (acc [+ res]) * [mask > 0], the mask quads requested like the residual's.
 // d.transposed (stride 1): the data gradient of a 3x3 / pad 1 conv - the same launch with the taps' windows mirrored.
-template <int WM, int WN, int FN, int STRIDE, bool RES, int TR = 0>
-__global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
+// NPL (planes multiplied per operand): 2 = the fp16 scheme (h + l, three products per fp32 product); 1 = the opt-in fast policy
+// (EGR_W_F16X1, DESIGN.md 5k, forward launches only): the loading waves write the high plane h = f16(x 2^e) alone, the multiplying waves
+// read the h fragments of the SAME two-plane weight image (the l fragments are skipped, never fetched) and issue one product.  Pre-scale,
+// descale, epilogue, hand-over, tile walk and the abs-max record are the same code.
+template <int WM, int WN, int FN, int STRIDE, bool RES, int TR, int NPL>
+__device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
     static_assert(WM * WN == 4 && (STRIDE == 0 || STRIDE == 1 || STRIDE == 2) && (FN == 1 || FN == 2), "four multiplying waves");
     static_assert(TR == 0 || (STRIDE != 0 && (FN == 1 || (TR == 1 && STRIDE == 1))), "training epilogues: the narrow wave tile (registers), statistics also on the wide one");
+    static_assert(NPL == 2 || (NPL == 1 && TR == 0), "one product: forward launches only");
     constexpr bool BNST = TR == 1, MASK = TR == 2;
-    constexpr int NPL = 2, NPR = 3, FM = 4;
+    constexpr int NPR = split_npr(NPL), FM = 4;
+    constexpr int WPL = 2;                                    // planes of the weight image (egr_pack_wh2_f32), whatever NPL multiplies
     constexpr bool PW = STRIDE == 0;
     constexpr bool WHOLE = FN == 1;                           // the staging area holds the whole tile
     constexpr int BM = WM * 128, BN = WN * 32 * FN, NFB = BN / 32;
@@ -172,8 +178,9 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
             for (int i = 0; i < NUH; ++i) {
-                unsigned h0, l0, h1, l1;
-                split4_f16(__uint_as_float(xr[SET][i][0]), __uint_as_float(xr[SET][i][1]), __uint_as_float(xr[SET][i][2]), __uint_as_float(xr[SET][i][3]), sa, h0, l0, h1, l1);
+                unsigned h0, l0 = 0, h1, l1 = 0;
+                if constexpr (NPL == 1) cvt4_f16(__uint_as_float(xr[SET][i][0]), __uint_as_float(xr[SET][i][1]), __uint_as_float(xr[SET][i][2]), __uint_as_float(xr[SET][i][3]), sa, h0, h1);
+                else split4_f16(__uint_as_float(xr[SET][i][0]), __uint_as_float(xr[SET][i][1]), __uint_as_float(xr[SET][i][2]), __uint_as_float(xr[SET][i][3]), sa, h0, l0, h1, l1);
                 if (lt + 256 * i < SEGS * HPX) {
                     // plane layout [8-channel half][pixel][8 channels]: the lanes of an A fragment (consecutive pixels, one half) read
                     // consecutive 16-byte slots - no bank conflicts (pixel-major 32-byte rows were 2-way for ds_read_b128).
@@ -181,7 +188,7 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
                     const int u = lt + 256 * i, px = PW ? u >> 4 : u >> 2, sg = PW ? u & 15 : u & 3;
                     uint8_t* dst = lb + buf * HBUF + (sg >> 2) * (NPL * PLANE) + ((sg >> 1) & 1) * (PLANE / 2) + px * 16 + (sg & 1) * 8;
                     *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
-                    *reinterpret_cast<u32x2*>(dst + PLANE) = u32x2{l0, l1};
+                    if constexpr (NPL == 2) *reinterpret_cast<u32x2*>(dst + PLANE) = u32x2{l0, l1};
                 }
             }
         };
@@ -479,15 +486,19 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
     // weight fragments: NSET register sets (a divisor of the nine taps, so that a tap's set is a compile-time constant), requested
     // AHEAD taps before they are multiplied.  L2 latency under load is above one microsecond: two taps of the narrow wave tile
     // (2 x 12 MFMAs = 768 cycles) do not cover it.
-    constexpr int NSET = PW ? 4 : (FN == 1 ? 9 : 3);
+    // One product: a tap is a third of the MFMAs, so the same lead in time needs more taps - and a set is half the registers: nine sets
+    // on both wave tiles, requested seven (narrow) / six (wide) taps ahead.
+    constexpr int NSET = PW ? 4 : ((FN == 1 || NPL == 1) ? 9 : 3);
 #ifndef TAPX_AHEAD1
 #define TAPX_AHEAD1 5
 #endif
-    constexpr int AHEAD = PW ? 3 : (FN == 1 ? TAPX_AHEAD1 : 2);
+    constexpr int AHEAD = PW ? 3 : (NPL == 1 ? (FN == 1 ? 7 : 6) : (FN == 1 ? TAPX_AHEAD1 : 2));
     static_assert(AHEAD < NSET && NT % NSET == 0, "weight register sets");
-    u32x4 af[FM][NPL], bf[NSET][FN][NPL];
+    // A fragments: NPL = 2 one register set per plane; NPL = 1 two sets of the one plane, tap t in set t & 1 (the next tap's fragments are
+    // requested in front of this tap's MFMAs - with a single set every tap would wait out the LDS latency)
+    u32x4 af[FM][2], bf[NSET][FN][NPL];
 
-    const int FSTR = a.ktiles * 2 * NPL * 1024;              // bytes between column fragments of the weight image
+    const int FSTR = a.ktiles * 2 * WPL * 1024;              // bytes between column fragments of the weight image
     struct WTile { __amdgpu_buffer_rsrc_t rb; int bvo; };
     auto wtile_of = [&](const Tile& T) __attribute__((always_inline)) {
         WTile W;
@@ -496,13 +507,13 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
         return W;
     };
     auto load_b_plane = [&](const WTile& W, int ck, int tap, int set, const int pl) __attribute__((always_inline)) {
-        const int so = PW ? (ck * 4 + tap) * NPL * 1024 : (((ck >> 1) * 9 + tap_w(tap)) * 2 * NPL + (ck & 1) * NPL) * 1024;
+        const int so = PW ? (ck * 4 + tap) * WPL * 1024 : (((ck >> 1) * 9 + tap_w(tap)) * 2 * WPL + (ck & 1) * WPL) * 1024;
 #pragma unroll
         for (int j = 0; j < FN; ++j) bf[set][j][pl] = __builtin_amdgcn_raw_buffer_load_b128(W.rb, W.bvo + j * FSTR + pl * 1024, so, 0);
     };
     auto load_b = [&](const WTile& W, int ck, int tap, int set) __attribute__((always_inline)) {
         load_b_plane(W, ck, tap, set, 0);
-        load_b_plane(W, ck, tap, set, 1);
+        if constexpr (NPL == 2) load_b_plane(W, ck, tap, set, 1);
     };
     // EARLY (experiment, off): a weight plane of tap T + NSET requested the moment its last product of tap T has been issued - products
     // in the order (l,h) (h,h) (h,l), so the h plane is free after the second product: 2 1/3 taps of lead instead of 2 for the wide wave
@@ -511,7 +522,7 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
 #ifndef TAPX_EARLY
 #define TAPX_EARLY 0
 #endif
-    constexpr bool EARLY = TAPX_EARLY && FN == 2;
+    constexpr bool EARLY = TAPX_EARLY && FN == 2 && NPL == 2;
     auto read_a = [&](int base, int tap, int pl) __attribute__((always_inline)) {
         const int to = tap_off(tap);
 #pragma unroll
@@ -520,7 +531,38 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
     // one chunk out of LDS buffer `base`; the weights of the position two taps ahead are requested in front of each tap's MFMAs
     // (X: the tile the chunk after this one belongs to, ckn its index there; behind the very last chunk they re-read the first
     // weights, harmlessly)
+    auto read_a1 = [&](int base, int tap, int slot) __attribute__((always_inline)) {      // NPL = 1: the one plane into register set `slot`
+        const int to = tap_off(tap);
+#pragma unroll
+        for (int i = 0; i < FM; ++i) af[i][slot] = *reinterpret_cast<const u32x4*>(lb + base + abase[i] + to);
+    };
     auto chunk = [&](int base, int ck, const WTile& W, const WTile& X, int ckn) __attribute__((always_inline)) {
+        if constexpr (NPL == 1) {
+            read_a1(base, 0, 0);
+#pragma unroll
+            for (int tap = 0; tap < NT; ++tap) {
+                const int pc = tap % NSET, pn = (tap + AHEAD) % NSET;
+#ifndef TAPX_EXP_NOB
+                if (tap + AHEAD < NT) load_b(W, ck, tap + AHEAD, pn);
+                else load_b(X, ckn, tap + AHEAD - NT, pn);
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+#ifndef TAPX_EXP_NOA
+                if (tap + 1 < NT) {
+                    read_a1(base, tap + 1, (tap + 1) & 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#endif
+#pragma unroll
+                for (int i = 0; i < FM; ++i)
+#pragma unroll
+                    for (int j = 0; j < FN; ++j) {
+                        acc[i][j] = mfma_split<2>(af[i][tap & 1], bf[pc][j][0], acc[i][j]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            }
+            return;
+        }
         read_a(base, 0, 1);
         read_a(base, 0, 0);
         constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, EARLY ? 0 : 1, EARLY ? 1 : 0};
@@ -550,7 +592,7 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
                             acc[i][j][4] = c1[0]; acc[i][j][5] = c1[1]; acc[i][j][6] = c1[2]; acc[i][j][7] = c1[3];
                         }
 #else
-                        acc[i][j] = mfma_split<NPL>(af[i][PA[t]], bf[pc][j][PB[t]], acc[i][j]);
+                        acc[i][j] = mfma_split<2>(af[i][PA[t]], bf[pc][j][NPL == 2 ? PB[t] : 0], acc[i][j]);
 #endif
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -635,6 +677,22 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
         unsigned long long* o = a.dbg + ((int64_t)bid * 8 + wave) * 8;
         o[0] = c_mul; o[1] = c_bar; o[2] = c_park; o[3] = TAPX_T() - c_t0; o[4] = (unsigned long long)my_tiles * NC;
     }
+}
+
+template <int WM, int WN, int FN, int STRIDE, bool RES, int TR = 0>
+__global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
+    conv_tapx_body<WM, WN, FN, STRIDE, RES, TR, 2>(a);
+}
+
+// The one-product form.  Its launch arguments are ConvArgs in a type of their own: the kernels that take a bare ConvArgs are the
+// library's default-policy set, which tools/conv_plan_cases.py lists by that signature and tests/test_conv_plan.py holds to its table -
+// no default launch reaches this kernel (tests/test_fast_policy_host.py covers its plans).
+struct ConvArgsFast {
+    ConvArgs a;
+};
+template <int WM, int WN, int FN, int STRIDE, bool RES>
+__global__ __launch_bounds__(512) void conv_tapx_f16_kernel(const ConvArgsFast f) {
+    conv_tapx_body<WM, WN, FN, STRIDE, RES, 0, 1>(f.a);
 }
 
 }  // namespace
@@ -722,6 +780,10 @@ bool plan_tapx(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
     int64_t wgs = k.tapx_blocks;
     if (k.tapx_tpw > 0 && tiles / k.tapx_tpw > wgs) wgs = (tiles / k.tapx_tpw + 7) / 8 * 8;
     out = plan_tile(p, EGR_ROUTE_TAPX, bm, bn, 100 * tr + 10 * (d.res_mode != EGR_RES_NONE) + cfg, 512);
+    if (p.h1 && tr == 0 && !d.transposed) {     // EGR_W_F16X1: forward launches multiply the high planes only (same tile, same grid)
+        out.variant += 1000;
+        out.planes = 1;
+    }
     out.grid_x = (int32_t)(tiles < wgs ? tiles : wgs);
     out.grid_z = 1;
     out.persistent = tiles > wgs;
@@ -757,6 +819,27 @@ int launch_tapx(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t stream
         case 203: return go(conv_tapx_kernel<2, 2, 1, 1, false, 2>);
         case 211: return go(conv_tapx_kernel<1, 4, 1, 1, true, 2>);
         case 213: return go(conv_tapx_kernel<2, 2, 1, 1, true, 2>);
+        default: break;
+    }
+    auto go1 = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x), dim3((unsigned)pl.block), 0, stream, ConvArgsFast{a});
+        return egr_launch_status();
+    };
+    switch (pl.variant) {    // 1000 + 10 R + cfg: one product (planes = 1), forward only; <WM, WN, FN, STRIDE, RES>
+        case 1000: return go1(conv_tapx_f16_kernel<2, 2, 2, 1, false>);
+        case 1001: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, false>);
+        case 1003: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, false>);
+        case 1004: return go1(conv_tapx_f16_kernel<1, 4, 2, 2, false>);
+        case 1005: return go1(conv_tapx_f16_kernel<1, 4, 1, 2, false>);
+        case 1006: return go1(conv_tapx_f16_kernel<1, 4, 2, 0, false>);
+        case 1007: return go1(conv_tapx_f16_kernel<1, 4, 1, 0, false>);
+        case 1010: return go1(conv_tapx_f16_kernel<2, 2, 2, 1, true>);
+        case 1011: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, true>);
+        case 1013: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, true>);
+        case 1014: return go1(conv_tapx_f16_kernel<1, 4, 2, 2, true>);
+        case 1015: return go1(conv_tapx_f16_kernel<1, 4, 1, 2, true>);
+        case 1016: return go1(conv_tapx_f16_kernel<1, 4, 2, 0, true>);
+        case 1017: return go1(conv_tapx_f16_kernel<1, 4, 1, 0, true>);
         default: return EGR_EINVAL;
     }
 }

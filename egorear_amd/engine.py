@@ -58,12 +58,12 @@ W6_MAX_ELEMS = 1 << 24
 
 def _w_operand(w: Optional[torch.Tensor]):
     """The weight operand under the active policy: w itself ("f32", or a shape the split kernels do not take), its bf16x3 image,
-    and for "f16x2" that image with its fp16 companion."""
+    and for "f16x2" (and "f16", the fast policy on the same operands) that image with its fp16 companion."""
     fmt = hip.policy().w_format
-    if w is None or fmt not in ("bf16x3", "f16x2") or not w.is_cuda or w.shape[-1] % 32 != 0 or w.shape[-2] * w.shape[-1] > W6_MAX_ELEMS:
+    if w is None or fmt not in ("bf16x3", "f16x2", "f16") or not w.is_cuda or w.shape[-1] % 32 != 0 or w.shape[-2] * w.shape[-1] > W6_MAX_ELEMS:
         return w
     w6 = hip.pack_w6(w)
-    return hip.add_wh2(w6) if fmt == "f16x2" else w6
+    return hip.add_wh2(w6) if hip.policy().fp16_scheme else w6
 
 
 def _npad(cout: int) -> int:
@@ -202,7 +202,7 @@ class State:
         self.packs: Dict[object, object] = share.packs if share is not None else {}
         self.workspace = torch.empty(_WORKSPACE_FLOATS, device=device, dtype=torch.float32)
         # abs-max records of the forward's activations (hip.AmaxArena): the pre-scales of the fp16-scheme launches come from them
-        self.amax = hip.AmaxArena(device) if hip.policy().w_format == "f16x2" else None
+        self.amax = hip.AmaxArena(device) if hip.policy().fp16_scheme else None
 
     def begin_forward(self):
         if self.amax is not None:
@@ -511,7 +511,7 @@ def run_backbone(st: State, encs, img: torch.Tensor, view0: int, nviews: int, fe
     # the other convolutions, egr_stem_conv7x7_x6_f32) when the shape fits its tile of 16 x 32 output pixels, else - and under the
     # "f32" weight format - on fp32 MFMA (egr_stem_conv7x7_pool_f32, tile 8 x 32)
     if hip.policy().w_format != "f32" and img.shape[3] % 32 == 0 and img.shape[4] % 64 == 0:
-        if hip.policy().w_format == "f16x2":       # the fp16 scheme (per-tile pre-scale of the input patch)
+        if hip.policy().fp16_scheme:               # the fp16 scheme (per-tile pre-scale of the input patch)
             wh2, wds = st.get((id(t0.layer_s2), "wh2"), lambda: hip.pack_stem_wh2(wp))
             x = hip.stem_x6(img, view0, nviews, wh2, sc, sh, groups=G, pool=True, w_descale=wds, amax_out=st.new_amax())
         else:
@@ -930,7 +930,7 @@ def _pack_pose3d(p3) -> PPose:
     w0p = w0.view(n_out, V, 128, 8, 8).permute(0, 1, 3, 4, 2).reshape(n_out, -1)
     P.mlp0 = P.mlp0_ws = None
     P.mlp0_src = (w0p, p3.mlp_pred[0][0].bias)
-    if hip.policy().w_format == "f16x2" and n_out % 64 == 0 and w0p.shape[1] % 256 == 0:
+    if hip.policy().fp16_scheme and n_out % 64 == 0 and w0p.shape[1] % 256 == 0:
         # the weight-stream launch (egr_linear_wstream_f32): two fp16 planes at the same 4 bytes per weight
         img, ds = hip.pack_wstream(w0p.float().contiguous())
         P.mlp0_ws = (img, ds, p3.mlp_pred[0][0].bias.detach().float().contiguous())

@@ -29,6 +29,17 @@ import sys
 import types
 
 
+class _on_default:
+    """A method that also answers on the class, for the default policy: LaunchPolicy.fast() is LaunchPolicy().fast()."""
+
+    def __init__(self, fn):
+        self.fn = fn
+        self.__doc__ = fn.__doc__
+
+    def __get__(self, obj, cls):
+        return types.MethodType(self.fn, obj if obj is not None else cls())
+
+
 @dataclasses.dataclass
 class LaunchPolicy:
     """Which kernel family a launch goes to - ONE object instead of module globals (round 6).  A module (engine.set_policy) or a
@@ -36,7 +47,8 @@ class LaunchPolicy:
     which is made from the environment at import.  The historical module attributes (hip.H2, hip.X6_MIN_ROWS, hip.CHAIN_*,
     engine.W_FORMAT, engine.LAYER_H2, engine.FUSED_*) are properties onto it: reading one returns the ACTIVE policy's value,
     assigning one changes the process default (what the parity tests that sweep launch rules do)."""
-    # weight operand of the implicit-GEMM launches: "f16x2" = bf16x3 image + fp16 companion, "bf16x3", "f32" (engine._w_operand)
+    # weight operand of the implicit-GEMM launches: "f16x2" = bf16x3 image + fp16 companion, "bf16x3", "f32" (engine._w_operand);
+    # "f16" = the operands of "f16x2" with the one-product bit on the conv launches (fast(), opt-in: outside the parity contract)
     w_format: str = "f16x2"
     # the fp16 scheme for the launches whose input carries an abs-max record (EGR_W_FORMAT=bf16x3 / f32 switch it off)
     h2: bool = True
@@ -66,12 +78,13 @@ class LaunchPolicy:
     def from_env(cls, env=None) -> "LaunchPolicy":
         e = os.environ if env is None else env
         fmt = e.get("EGR_W_FORMAT", "f16x2")
-        return cls(w_format=fmt, h2=fmt == "f16x2",
+        fp16 = fmt in ("f16x2", "f16")
+        return cls(w_format=fmt, h2=fp16,
                    x6_min_rows=int(e.get("EGR_X6_MIN_ROWS", "4096")), x6_min_flops=float(e.get("EGR_X6_MIN_FLOPS", "5e8")),
                    x6_train_min_rows=int(e.get("EGR_X6_TRAIN_MIN_ROWS", "8192")), x6_train_min_flops=float(e.get("EGR_X6_TRAIN_MIN_FLOPS", "4e9")),
                    chain=e.get("EGR_CONV_CHAIN", "1") != "0", chain_min_rows=int(e.get("EGR_CONV_CHAIN_MIN_ROWS", "8192")),
                    chain_big=e.get("EGR_CONV_CHAIN_BIG", "1") != "0", chain_big_min_rows=int(e.get("EGR_CONV_CHAIN_BIG_MIN_ROWS", "65536")),
-                   wgrad_x6=fmt != "f32", layer_h2=fmt == "f16x2" and e.get("EGR_LAYER_H2", "1") != "0",
+                   wgrad_x6=fmt != "f32", layer_h2=fp16 and e.get("EGR_LAYER_H2", "1") != "0",
                    fused_layer=e.get("EGR_FUSED_LAYER", "1") != "0", fused_query=e.get("EGR_FUSED_QUERY", "1") != "0")
 
     def replace(self, **kw) -> "LaunchPolicy":
@@ -85,6 +98,20 @@ class LaunchPolicy:
     def exact(self) -> "LaunchPolicy":
         """The exact-operand arithmetic (EGR_W_FORMAT=bf16x3): three bf16 planes, six products, fused layers on the fp32 matrix cores."""
         return self.replace(w_format="bf16x3", h2=False, layer_h2=False)
+
+    @_on_default
+    def fast(self) -> "LaunchPolicy":
+        """The half-precision serving arithmetic (EGR_W_FORMAT=f16), opt-in and outside the parity contract: the forward launches of the
+        role-split conv kernel multiply the fp16 scheme's HIGH planes only - fp16-rounded operands, one matrix product instead of
+        three, fp32 accumulation (EGR_W_F16X1).  Same packs and records as "f16x2" (made again under this policy's own
+        pack_key); every launch without a one-product kernel - stem, chains, fused layers, weight stream, small launches - runs what
+        it runs under the default policy.  The training step ignores the bit: it computes what it computes under "f16x2"."""
+        return self.replace(w_format="f16", h2=True, layer_h2=True)
+
+    @property
+    def fp16_scheme(self) -> bool:
+        """The weight format carries the fp16 companion images ("f16x2", or "f16" on top of it)."""
+        return self.w_format in ("f16x2", "f16")
 
 
 POLICY = LaunchPolicy.from_env()       # the process default
@@ -173,6 +200,8 @@ class ConvPlan(C.Structure):
 
 # egr_conv_route: the values of ConvPlan.route and of conv_last_kernel()
 ROUTE_F32_TILED, ROUTE_SPLIT_TILED, ROUTE_TAP, ROUTE_TAP2, ROUTE_STREAM_1X1, ROUTE_SMALL_F32, ROUTE_TAPX = range(7)
+# egr_conv_desc.w_format bits the wrappers set by name (include/egorear_hip.h)
+W_F16X2, W_F16X1 = 4, 8
 
 
 class ChainAux(C.Structure):
@@ -322,6 +351,9 @@ def _check(rc: int, name: str):
 # When PROFILE is a list, every launch is bracketed by HIP events recorded on the launch stream (torch's current
 # stream) and (kernel name, start, end, algorithmic work) is appended; bench.py uses this for the roofline leg.
 PROFILE = None
+# When PLAN_LOG is a list, every forward conv2d launch first asks egr_conv_plan what it is about to launch and appends
+# (tag, ConvPlan): which launches of a forward took which route / variant / plane count (tests, tools/fast_bench.py).
+PLAN_LOG = None
 
 
 # Device of the launch being assembled: set by the first tensor handed to _p(), checked for every further one, consumed by
@@ -613,7 +645,7 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
            split_k: int = 1, groups: int = 1, gx: Optional[int] = None, gy: Optional[int] = None,
            gr: Optional[int] = None, grs: int = 0, grm: int = 0, transposed_out_hw: Optional[tuple] = None, x6_min: Optional[tuple] = None,
            mask: Optional[Img] = None, amax_out: Optional[torch.Tensor] = None, amax_arena: Optional["AmaxArena"] = None,
-           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None) -> Optional[Img]:
+           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None, one_product: Optional[bool] = None) -> Optional[Img]:
     """Implicit-GEMM conv / linear.  Output goes to `out` (NHWC Img, maybe a channel slice), or to the raw
     tensor `out_nchw` (channel-major planes placed by `ymap`), or to a fresh NHWC tensor.
 
@@ -669,6 +701,11 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     wptr = (_p(w.h2, torch.float16) if h2 else _p(w.img, torch.bfloat16)) if x6 else _p(_cont(w, "packed weight"))
     d = ConvDesc()
     d.w_format = (4 if h2 else 1) if x6 else 0
+    # the fast policy (or one_product=True: tests): the same operands plus EGR_W_F16X1 - the dispatch takes a one-product kernel where
+    # one exists (plan.planes == 1) and treats the bit as absent everywhere else
+    h1 = h2 and (pol.w_format == "f16" if one_product is None else bool(one_product))
+    if h1:
+        d.w_format |= W_F16X1
     d.n, d.h, d.w, d.cin, d.cout = x.n, x.h, x.w, x.c, cout
     d.kh, d.kw, d.stride, d.pad, d.ho, d.wo = kh, kw, stride, pad, ho, wo
     d.ldx = x.ld
@@ -756,7 +793,14 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
             aux.bn_partials = _p(bn_ws, torch.float64).value
             aux.bn_tiles_out = C.addressof(tiles)
             aux.bn_capacity = bn_ws.numel()
-    fmt = "h2 " if h2 else ("x6 " if x6 else "")
+    fmt = ("h1 " if h1 else "h2 ") if h2 else ("x6 " if x6 else "")
+    if PLAN_LOG is not None:
+        dev, plan = _DEV[0], ConvPlan()
+        _check(lib.egr_conv_plan(C.byref(d), _p(x.t), wptr, _p(scale), _p(shift), _p(res.t) if res is not None else None, _p(rowscale),
+                                 _p(rowmask, torch.uint8), None, yptr, ws_ptr, ws_n, C.byref(aux) if aux is not None else None, C.byref(plan)),
+               "egr_conv_plan")
+        _DEV[0] = dev
+        PLAN_LOG.append((f"{fmt}G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}", plan))
     _launch("egr_conv2d_nhwc_f32", lib.egr_conv2d_nhwc_ex_f32, C.byref(d), _p(x.t), wptr, _p(scale), _p(shift),
             _p(res.t) if res is not None else None, _p(rowscale), _p(rowmask, torch.uint8), yptr, ws_ptr, ws_n,
             C.byref(aux) if aux is not None else None, _stream(),

@@ -44,8 +44,9 @@ OVERLAP = True          # the leaves of the reverse pass on a second stream (Ste
 
 
 def _conv2d(*a, **k):
-    """hip.conv2d under the training step's split-launch rule (hip.X6_TRAIN_MIN_*)."""
-    return hip.conv2d(*a, x6_min=(hip.policy().x6_train_min_rows, hip.policy().x6_train_min_flops), **k)
+    """hip.conv2d under the training step's split-launch rule (hip.X6_TRAIN_MIN_*).  The step keeps its own arithmetic: under the fast
+    policy (hip.LaunchPolicy.fast) it ignores the one-product bit and computes what it computes under "f16x2"."""
+    return hip.conv2d(*a, x6_min=(hip.policy().x6_train_min_rows, hip.policy().x6_train_min_flops), one_product=False, **k)
 
 
 def _ceil32(n: int) -> int:
@@ -88,7 +89,7 @@ class PackCache:
         # abs-max records of one step's activations and gradients, for the fp16 scheme: forward and data-gradient
         # launches above the split threshold take the two-plane fp16 images of their weight operands (the graph of a captured step
         # holds pointers into it)
-        self.amax = hip.AmaxArena(device, records=1024) if (hip.policy().h2 and hip.policy().w_format == "f16x2") else None
+        self.amax = hip.AmaxArena(device, records=1024) if (hip.policy().h2 and hip.policy().fp16_scheme) else None
         self.sources: Dict[int, tuple] = {}  # id(param) -> (param, data_ptr)
         self.ready = False
 
@@ -888,7 +889,7 @@ def backbone_train(S: Step, encs, img: torch.Tensor, view0: int, nviews: int):
     # pack every step: one tiny launch
     pol = hip.policy()
     if pol.w_format != "f32" and H % 32 == 0 and W % 64 == 0:
-        if pol.h2 and pol.w_format == "f16x2":
+        if pol.h2 and pol.fp16_scheme:
             bank, wds = hip.pack_stem_wh2(wp)
             x = hip.stem_x6(img, view0, nviews, bank, None, None, groups=G, w_descale=wds).t
         else:

@@ -91,7 +91,12 @@ typedef struct {
 } egr_conv_desc;
 enum { EGR_W_F32 = 0, EGR_W_BF16X3 = 1,
        EGR_W_FORCE = 2 /* egr_conv2d_wgrad_f32 only: with EGR_W_BF16X3, take the split kernel whatever the problem size (tests) */,
-       EGR_W_F16X2 = 4 /* egr_conv2d_nhwc_ex_f32 only: w is the image egr_pack_wh2_f32 made (two fp16 planes per weight) */ };
+       EGR_W_F16X2 = 4 /* egr_conv2d_nhwc_ex_f32 only: w is the image egr_pack_wh2_f32 made (two fp16 planes per weight) */,
+       /* With EGR_W_F16X2 (egr_conv2d_nhwc_ex_f32 / egr_conv_plan; EGR_EINVAL with any other format): the opt-in fast policy (DESIGN.md
+        * §5k).  w is the same F16X2 image; where a one-product kernel exists - the forward launches of the role-split route - both
+        * operands are multiplied as their HIGH planes only, f16(x 2^e) f16(w 2^k), one matrix product instead of three: fp16-rounded
+        * operands (relative 2^-11 each), fp32 accumulation.  Every other launch treats the bit as absent. */
+       EGR_W_F16X1 = 8 };
 
 /* Split a packed fp32 weight matrix w (groups, npad, k) — npad = round_up(cout, 32), k = kh*kw*cin, k % 32 == 0 — into
  * the EGR_W_BF16X3 image: per group egr_w6_elems(npad, k) bf16 elements laid out
@@ -229,10 +234,12 @@ typedef struct {
      *   STREAM_1X1               100 KS + 10 NCF + RESK  (KS = cin / 16, NCF = 32-column fragments per workgroup, RESK 0 no residual /
      *                            1 residual / 2 residual upsampled on the fly)
      *   TAPX                     100 T + 10 R + cfg  (T 0 forward / 1 statistics epilogue / 2 masked data gradient, R 1 with residual,
-     *                            cfg = the kernel's (tile, wave tile, stride) configuration 0, 1, 3 .. 7)
+     *                            cfg = the kernel's (tile, wave tile, stride) configuration 0, 1, 3 .. 7); + 1000: the one-product
+     *                            form of a forward variant (EGR_W_F16X1)
      *   others                   0 */
     int32_t variant;
-    int32_t planes;              /* 16-bit planes per operand: 2 (EGR_W_F16X2), 3 (EGR_W_BF16X3), 0 (fp32) */
+    int32_t planes;              /* 16-bit planes multiplied per operand: 2 (EGR_W_F16X2), 3 (EGR_W_BF16X3), 0 (fp32); 1: a one-product
+                                  * launch (EGR_W_F16X1 on a TAPX forward variant) */
     int32_t tiles_m, tiles_n;    /* tiles per group */
     int32_t grid_x, grid_y, grid_z, block;     /* the main launch */
     int32_t split_k, ktiles_per_split;        /* K slices (1: none) of ktiles_per_split 32-deep chunks, none empty */

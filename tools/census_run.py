@@ -3,6 +3,8 @@
 policy against the CPU oracle - all arg-maxes of both heat-map sets, valid masks, four pose sets, tie exposure, float64 referee.
     python tools/census_run.py --frames 2048 --out census.json        (one line of progress per GPU batch)
     python tools/census_run.py --frames 512 --policies shipped,exact,f32 --referee f64 --out referee.json
+    python tools/census_run.py --frames 512 --policy shipped,fast,bf16x3 --out 'profiles/fast_policy_census_512_{policy}.json'
+                                              (one file per policy in the single-policy layout, same seeds, the oracle computed once)
 Test infrastructure (imports oracle/): not part of the product or of bench.py's timed region."""
 import argparse, copy, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,8 +21,9 @@ ap.add_argument("--seed0", type=int, default=100)
 ap.add_argument("--out", default="")
 ap.add_argument("--weight-seed", type=int, default=42, help="seed of the synthetic weights (egorear_amd/synth.py); the tests and bench.py use 42")
 ap.add_argument("--camera", default="ego4view_syn", choices=["ego4view_syn", "ego4view_rw"], help="camera model / config family (rw: with coord_trans_mat)")
-ap.add_argument("--policies", default="shipped", help="comma-separated launch policies the GPU forwards run under, on one module "
-                "(shipped = the process default, exact = bf16x3 six products, f32 = fp32 matrix cores); the oracle is computed once")
+ap.add_argument("--policies", "--policy", default="shipped", help="comma-separated launch policies the GPU forwards run under, on one module "
+                "(shipped = the process default, exact = bf16x3 = six products, f32 = fp32 matrix cores, fast = the opt-in one-product "
+                "policy of DESIGN.md 5k, whose counts are reported and never gated); the oracle is computed once")
 ap.add_argument("--referee", default="", choices=["", "f64"], help="f64: every map is also put before the float64 oracle (oracle/referee.py)")
 a = ap.parse_args()
 torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
@@ -30,7 +33,8 @@ sd = {k: v.clone() for k, v in net.state_dict().items()}
 net = net.to("cuda:0")
 cams = O.make_cameras(a.camera, os.path.join(os.path.dirname(os.path.abspath(synth.__file__)), "calib", "ego4view"))
 assert hip.H2 and hip.X6_MIN_ROWS > 0
-POLICIES = {"shipped": None, "exact": hip.POLICY.exact(), "f32": hip.POLICY.replace(w_format="f32", h2=False, layer_h2=False, wgrad_x6=False)}
+POLICIES = {"shipped": None, "exact": hip.POLICY.exact(), "bf16x3": hip.POLICY.exact(), "fast": hip.POLICY.fast(),
+            "f32": hip.POLICY.replace(w_format="f32", h2=False, layer_h2=False, wgrad_x6=False)}
 names = a.policies.split(",")
 assert names and all(n in POLICIES for n in names), a.policies
 acc, ref, t0 = {n: None for n in names}, {n: None for n in names}, time.time()
@@ -110,5 +114,8 @@ else:
             del st["f32_disagreements"], st["f32_valid_flips"]
         out["referee_f64"] = {"hip": ref, "f32_oracle": f32_ref, "rounding_gap": census.ROUNDING_GAP}
 print(json.dumps(out))
-if a.out:
+if "{policy}" in a.out:
+    for n in names:
+        json.dump(acc[n], open(a.out.replace("{policy}", n), "w"), indent=1)
+elif a.out:
     json.dump(out, open(a.out, "w"), indent=1)
