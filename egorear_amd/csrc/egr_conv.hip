@@ -2235,8 +2235,9 @@ int conv_check(const egr_conv_desc& d, const ConvOperands& o) {
     if ((d.xmap.stride_inner | d.xmap.stride_outer) % 4 != 0) return EGR_EINVAL;
     if (d.groups > 1 && ((d.gx | d.gw | d.gp | d.gy | d.gr) % 4 != 0)) return EGR_EINVAL;  // keep 16-byte alignment per group
     if (d.groups > 65535) return EGR_EINVAL;
-    const int fmt = d.w_format & ~EGR_W_F16X1;       // (the one-product bit rides on EGR_W_F16X2 only)
+    const int fmt = d.w_format & ~(EGR_W_F16X1 | EGR_W_F16X1T);      // (the one-product bits ride on EGR_W_F16X2 only, the training one on both)
     if ((fmt != EGR_W_F32 && fmt != EGR_W_BF16X3 && fmt != EGR_W_F16X2) || (fmt != d.w_format && fmt != EGR_W_F16X2)) return EGR_EINVAL;
+    if ((d.w_format & EGR_W_F16X1T) && !(d.w_format & EGR_W_F16X1)) return EGR_EINVAL;
     const bool h2 = fmt == EGR_W_F16X2, x6 = h2 || fmt == EGR_W_BF16X3;   // split kernels (bf16 x 3 / fp16 x 2)
     if (x6 && d.groups > 1 && d.gw % 8 != 0) return EGR_EINVAL;
     // the fp16 scheme needs the weights' descale and the activations' abs-max record
@@ -2276,7 +2277,7 @@ int conv_check(const egr_conv_desc& d, const ConvOperands& o) {
 void conv_geometry(ConvArgs& a, const egr_conv_desc& dd, const ConvOperands& o, unsigned long long* dbg) {
     a.d = dd;
     egr_conv_desc& d = a.d;
-    d.w_format &= ~EGR_W_F16X1;     // every route sees the plain format; the bit travels as ConvProblem.h1 (conv_run)
+    d.w_format &= ~(EGR_W_F16X1 | EGR_W_F16X1T);     // every route sees the plain format; the bits travel as ConvProblem.h1 / h1t (conv_run)
     if (d.groups <= 0) d.groups = 1;
     a.x = o.x; a.w = o.w; a.scale = o.scale; a.shift = o.shift; a.res = o.res; a.rowscale = o.rowscale; a.rowmask = o.rowmask;
     a.y = o.y; a.ws = o.workspace;
@@ -2598,7 +2599,8 @@ int conv_run(const egr_conv_desc* dd, const ConvOperands& o, egr_conv_plan_t* pl
     conv_geometry(a, *dd, o, g_dbg);
     const bool h2 = a.d.w_format == EGR_W_F16X2;
     const ConvProblem p = {a, y_span(a.d), a.d.res_mode ? r_span(a.d) : 0, o.workspace_floats, ((uintptr_t)o.workspace & 15) == 0,
-                           h2 || a.d.w_format == EGR_W_BF16X3, h2, h2 && (dd->w_format & EGR_W_F16X1) != 0};
+                           h2 || a.d.w_format == EGR_W_BF16X3, h2, h2 && (dd->w_format & EGR_W_F16X1) != 0,
+                           h2 && (dd->w_format & EGR_W_F16X1T) != 0};
     egr_conv_plan_t pl;
     if (const int rc = conv_plan(p, g_knobs, pl)) return rc;
     if (plan_only) {

@@ -87,7 +87,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 //            accumulators are multiplied by the inverse before the epilogue.  Half the matrix instructions and two thirds of
 //            the operand bytes of the bf16 scheme.
 //   NPL = 1 (EGR_W_F16X2 | EGR_W_F16X1, role-split kernel only): x 2^e = h alone, fp16-rounded operands, ONE product - the opt-in
-//            fast policy; the weight operand is the h plane of the two-plane image
+//            fast policy and, with EGR_W_F16X1T, its training side (5l); the weight operand is the h plane of the
+//            two-plane image
 constexpr int split_npr(int npl) { return npl == 3 ? 6 : (npl == 2 ? 3 : 1); }
 // plane of the A operand whose last use is product t (-1: none): its registers can be refilled for the next tap behind it
 constexpr int split_free_a(int npl, int t) {
@@ -211,6 +212,7 @@ struct ConvProblem {
     bool workspace_aligned;      // a.ws is 16-byte aligned
     bool x6, h2;                 // split kernels (bf16 x 3 / fp16 x 2); h2: the fp16 scheme
     bool h1;                     // EGR_W_F16X1 came with EGR_W_F16X2 (a.d.w_format holds the plain format): one product where a kernel has that form
+    bool h1t;                    // EGR_W_F16X1T came with both: the role-split route's training / data-gradient launches take it too
 };
 
 // A route has fixed its tile: the fields every route fills the same way (one workgroup per tile until the route says otherwise).

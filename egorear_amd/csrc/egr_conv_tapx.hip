@@ -45,6 +45,21 @@ namespace {
 #ifndef TAPX_PRIO
 #define TAPX_PRIO 0        // s_setprio of the multiplying waves
 #endif
+// amax_flush for the one-product training forms: the same fold, its shuffle addresses computed HERE from a lane index the compiler
+// cannot trace.  Shared with act_prescale's at the top of the kernel they stay live through the whole tile loop; with nine weight sets
+// and the statistics' registers on top, the two widest variants (1100, 1105) kept them in scratch: 24 bytes per lane, as their two-plane
+// forms do.  NOT a complete fix: 8 bytes remain on those two - one value stored in front of the tile loop and reloaded behind it for the
+// last slab write, nothing inside the loop - and the empty asm is a hint the register allocator is free to defeat: check
+// the resource-usage lines after a compiler update.
+__device__ __forceinline__ void amax_flush_late(unsigned* amax_out, float amx, int slot) {
+    int ln = threadIdx.x & 63;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        amx = fmaxf(amx, __int_as_float(__builtin_amdgcn_ds_bpermute((ln ^ o) << 2, __float_as_int(amx))));
+    if (ln == 0 && amx > 0.f)
+        __hip_atomic_fetch_max(amax_out + (slot & 63), __float_as_uint(amx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 constexpr int XOOB = (int)0x80000000;   // buffer offset beyond every descriptor's range: loads return 0, stores are dropped
 
 // pixels of one 16-bit plane of a chunk
@@ -66,14 +81,14 @@ constexpr int tapx_hp(int bm, int stride) { return stride == 2 ? 4 * tapx_cls(bm
 // M tile); 2 = data gradient behind a ReLU: dx = (acc [+ res]) * [mask > 0], the mask quads requested like the residual's.
 // d.transposed (stride 1): the data gradient of a 3x3 / pad 1 conv - the same launch with the taps' windows mirrored.
 // NPL (planes multiplied per operand): 2 = the fp16 scheme (h + l, three products per fp32 product); 1 = the opt-in fast policy
-// (EGR_W_F16X1, DESIGN.md 5k, forward launches only): the loading waves write the high plane h = f16(x 2^e) alone, the multiplying waves
+// (EGR_W_F16X1, DESIGN.md 5k: forward launches; EGR_W_F16X1T, 5l: the TR launches and the plain data gradients): the loading waves write the high plane h = f16(x 2^e) alone, the multiplying waves
 // read the h fragments of the SAME two-plane weight image (the l fragments are skipped, never fetched) and issue one product.  Pre-scale,
 // descale, epilogue, hand-over, tile walk and the abs-max record are the same code.
 template <int WM, int WN, int FN, int STRIDE, bool RES, int TR, int NPL>
 __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
     static_assert(WM * WN == 4 && (STRIDE == 0 || STRIDE == 1 || STRIDE == 2) && (FN == 1 || FN == 2), "four multiplying waves");
     static_assert(TR == 0 || (STRIDE != 0 && (FN == 1 || (TR == 1 && STRIDE == 1))), "training epilogues: the narrow wave tile (registers), statistics also on the wide one");
-    static_assert(NPL == 2 || (NPL == 1 && TR == 0), "one product: forward launches only");
+    static_assert(NPL == 2 || NPL == 1, "planes multiplied per operand");
     constexpr bool BNST = TR == 1, MASK = TR == 2;
     constexpr int NPR = split_npr(NPL), FM = 4;
     constexpr int WPL = 2;                                    // planes of the weight image (egr_pack_wh2_f32), whatever NPL multiplies
@@ -449,7 +464,11 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
             barrier();                                        // (the multiplying waves come to this one too)
             stats_reduce();
         }
-        if (a.amax_out) amax_flush(a.amax_out, amx, bid * 4 + wave);
+        if constexpr (NPL == 1 && TR != 0) {
+            if (a.amax_out) amax_flush_late(a.amax_out, amx, bid * 4 + wave);
+        } else {
+            if (a.amax_out) amax_flush(a.amax_out, amx, bid * 4 + wave);
+        }
         return;
     }
 
@@ -690,9 +709,9 @@ __global__ __launch_bounds__(512) void conv_tapx_kernel(const ConvArgs a) {
 struct ConvArgsFast {
     ConvArgs a;
 };
-template <int WM, int WN, int FN, int STRIDE, bool RES>
+template <int WM, int WN, int FN, int STRIDE, bool RES, int TR = 0>
 __global__ __launch_bounds__(512) void conv_tapx_f16_kernel(const ConvArgsFast f) {
-    conv_tapx_body<WM, WN, FN, STRIDE, RES, 0, 1>(f.a);
+    conv_tapx_body<WM, WN, FN, STRIDE, RES, TR, 1>(f.a);
 }
 
 }  // namespace
@@ -780,7 +799,9 @@ bool plan_tapx(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
     int64_t wgs = k.tapx_blocks;
     if (k.tapx_tpw > 0 && tiles / k.tapx_tpw > wgs) wgs = (tiles / k.tapx_tpw + 7) / 8 * 8;
     out = plan_tile(p, EGR_ROUTE_TAPX, bm, bn, 100 * tr + 10 * (d.res_mode != EGR_RES_NONE) + cfg, 512);
-    if (p.h1 && tr == 0 && !d.transposed) {     // EGR_W_F16X1: forward launches multiply the high planes only (same tile, same grid)
+    // EGR_W_F16X1: forward launches multiply the high planes only (same tile, same grid); EGR_W_F16X1T: the training launches too -
+    // statistics epilogue, masked data gradient, and the plain data gradient (a forward variant on the transposed weight image)
+    if (tr == 0 && !d.transposed ? p.h1 : p.h1t) {
         out.variant += 1000;
         out.planes = 1;
     }
@@ -825,7 +846,7 @@ int launch_tapx(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t stream
         hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x), dim3((unsigned)pl.block), 0, stream, ConvArgsFast{a});
         return egr_launch_status();
     };
-    switch (pl.variant) {    // 1000 + 10 R + cfg: one product (planes = 1), forward only; <WM, WN, FN, STRIDE, RES>
+    switch (pl.variant) {    // 1000 + 100 TR + 10 R + cfg: one product (planes = 1); <WM, WN, FN, STRIDE, RES, TR>
         case 1000: return go1(conv_tapx_f16_kernel<2, 2, 2, 1, false>);
         case 1001: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, false>);
         case 1003: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, false>);
@@ -840,6 +861,14 @@ int launch_tapx(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t stream
         case 1015: return go1(conv_tapx_f16_kernel<1, 4, 1, 2, true>);
         case 1016: return go1(conv_tapx_f16_kernel<1, 4, 2, 0, true>);
         case 1017: return go1(conv_tapx_f16_kernel<1, 4, 1, 0, true>);
+        case 1100: return go1(conv_tapx_f16_kernel<2, 2, 2, 1, false, 1>);
+        case 1101: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, false, 1>);
+        case 1103: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, false, 1>);
+        case 1105: return go1(conv_tapx_f16_kernel<1, 4, 1, 2, false, 1>);
+        case 1201: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, false, 2>);
+        case 1203: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, false, 2>);
+        case 1211: return go1(conv_tapx_f16_kernel<1, 4, 1, 1, true, 2>);
+        case 1213: return go1(conv_tapx_f16_kernel<2, 2, 1, 1, true, 2>);
         default: return EGR_EINVAL;
     }
 }

@@ -256,9 +256,16 @@ __device__ __forceinline__ void wg_prescale(const unsigned* rec, int lane, float
     s = __uint_as_float((unsigned)(127 + k) << 23);
     inv = __uint_as_float((unsigned)(127 - k) << 23);
 }
+// NPL = 1 (EGR_W_F16X1 beside the fp16 scheme's bits; DESIGN.md 5l, outside the parity contract): the HIGH plane of both operands alone,
+// h = f16(v s) - the first half of wg_split2_f16 - and ONE product per fragment pair.  Same records, same pre-scales, same descale, the
+// stage one plane per operand.
+__device__ __forceinline__ void wg_cvt2_f16(float v0, float v1, float s, unsigned& h) {
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(v0), "v"(s));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(v1), "v"(s));
+}
 template <int NPL>
 __device__ __forceinline__ f32x16 wg_mfma(const wg_bf16x8& x, const wg_bf16x8& y, const f32x16& c) {
-    if constexpr (NPL == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, x), __builtin_bit_cast(wg_f16x8, y), c, 0, 0, 0);
+    if constexpr (NPL <= 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, x), __builtin_bit_cast(wg_f16x8, y), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0);
 }
 
@@ -271,7 +278,7 @@ __device__ __forceinline__ void* wg_uniform_ptr(const void* p) {
 
 template <int BCO, int NPL = 3>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a) {
-    constexpr int NPR = NPL == 2 ? 3 : 6, SPU = NPL == 2 ? 3 : 5;   // matrix instructions per fp32 product; staging steps per unit
+    constexpr int NPR = NPL == 1 ? 1 : (NPL == 2 ? 3 : 6), SPU = NPL <= 2 ? 3 : 5;   // matrix instructions per fp32 product; staging steps per unit
     constexpr int PS = 16;                                       // pixels per stage = one k16 step
     constexpr int TM = BCO / 2, FM = TM / 32, FN = 2;            // waves 2 (co) x 2 (k); wave tile TM x 64
     constexpr int ROW_DY = 2 * BCO + 64, ROW_A = 2 * BKO + 64;   // bytes per pixel row of a plane
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     float s_dy = 1.f, s_x = 1.f, dsc = 1.f;
-    if constexpr (NPL == 2) {
+    if constexpr (NPL <= 2) {
         float i_dy, i_x;
         wg_prescale(a.amax_dy, lane, s_dy, i_dy);
         wg_prescale(a.amax_x, lane, s_x, i_x);
@@ -390,7 +397,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a
         constexpr int BUF = decltype(buf_tag)::value;
         const int u = k / SPU, q = k % SPU;
         if (q == 0 && u < ND && do_bias) bacc += xr[SET][u];
-        if constexpr (NPL == 2) {      // steps 0/1: the unit's two pairs, 2: the writes
+        if constexpr (NPL == 1) {      // steps 0/1: the high parts of the unit's two pairs, 2: the write
+            if (q < 2) {
+                wg_cvt2_f16(xr[SET][u][2 * q], xr[SET][u][2 * q + 1], u < ND ? s_dy : s_x, sh_[u][q]);
+            } else {
+                uint8_t* dst;
+                if (u < ND) dst = lds + BUF * STB + (d_pix + (256 / SEG_DY) * u) * ROW_DY + d_seg * 8;
+                else dst = lds + BUF * STB + NPL * PL_DY + (a_pix + 8 * (u - ND)) * ROW_A + (a_chunk * 32 + a_seg * 4) * 2;
+                *reinterpret_cast<wg_u32x2*>(dst) = wg_u32x2{sh_[u][0], sh_[u][1]};
+            }
+        } else if constexpr (NPL == 2) {      // steps 0/1: the unit's two pairs, 2: the writes
             if (q < 2) {
                 wg_split2_f16(xr[SET][u][2 * q], xr[SET][u][2 * q + 1], u < ND ? s_dy : s_x, sh_[u][q], sl_[u][q]);
             } else {
@@ -456,7 +472,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a
         for (int j = 0; j < FN; ++j)
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) bf[j][pl] = frag(st + NPL * PL_DY + pl * PL_A, ROW_A, wn * 64 + 32 * j);
-        constexpr int PA[6] = {NPL == 2 ? 1 : 2, 0, NPL == 2 ? 0 : 1, 1, 0, 0}, PB[6] = {0, NPL == 2 ? 1 : 2, NPL == 2 ? 0 : 1, 0, 1, 0};
+        constexpr int PA[6] = {NPL == 1 ? 0 : (NPL == 2 ? 1 : 2), 0, NPL == 2 ? 0 : 1, 1, 0, 0}, PB[6] = {0, NPL == 2 ? 1 : 2, NPL == 2 ? 0 : 1, 0, 1, 0};
         int n = 0, done = 0;
 #pragma unroll
         for (int t = 0; t < NPR; ++t)
@@ -545,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + wm * TM + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (co < a.cout) wsg[((int64_t)split * a.cout + co) * a.K + kcol] = NPL == 2 ? acc[i][j][r] * dsc : acc[i][j][r];
+                if (co < a.cout) wsg[((int64_t)split * a.cout + co) * a.K + kcol] = NPL <= 2 ? acc[i][j][r] * dsc : acc[i][j][r];
             }
         }
 }
@@ -560,7 +576,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x6_kernel(const WgradArgs a
 // instructions per MFMA instead of 11.  Rows are requested at the start of a stage and split behind its second third.
 template <int CO_T, int CB_T, int WS, int NPL = 3>
 __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs a) {
-    constexpr int NPR = NPL == 2 ? 3 : 6, SPU = NPL == 2 ? 3 : 5;
+    constexpr int NPR = NPL == 1 ? 1 : (NPL == 2 ? 3 : 6), SPU = NPL <= 2 ? 3 : 5;
     constexpr int PS = 16;                                       // output pixels per stage: PS / WS image rows of WS pixels
     constexpr int XP = WS + 2, XR = PS / WS + 2;                 // input pixels per row / input rows, with the halo
     static_assert(WS == 16 || WS == 8, "16 pixels of one row, or two rows of an 8-pixel-wide image");
@@ -576,7 +592,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float s_dy = 1.f, s_x = 1.f, dsc = 1.f;
-    if constexpr (NPL == 2) {
+    if constexpr (NPL <= 2) {
         float i_dy, i_x;
         wg_prescale(a.amax_dy, lane, s_dy, i_dy);
         wg_prescale(a.amax_x, lane, s_x, i_x);
@@ -639,7 +655,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
     float ra_[NUN][2], rb_[NUN][2];
     auto slice = [&](int base, int k) {
         const int u = k / SPU, q = k % SPU;
-        if constexpr (NPL == 2) {
+        if constexpr (NPL == 1) {
+            if (q < 2) {
+                wg_cvt2_f16(xr[u][2 * q], xr[u][2 * q + 1], u < ND ? s_dy : s_x, sh_[u][q]);
+            } else if (u < ND || NX * 256 == UX || tid + 256 * (u - ND) < UX) {
+                uint8_t* const dst = u < ND ? lds + base + d_lds[u] : lds + base + NPL * PL_DY + x_lds[u - ND];
+                *reinterpret_cast<wg_u32x2*>(dst) = wg_u32x2{sh_[u][0], sh_[u][1]};
+            }
+        } else if constexpr (NPL == 2) {
             if (q < 2) {
                 wg_split2_f16(xr[u][2 * q], xr[u][2 * q + 1], u < ND ? s_dy : s_x, sh_[u][q], sl_[u][q]);
             } else if (u < ND || NX * 256 == UX || tid + 256 * (u - ND) < UX) {
@@ -691,7 +714,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
     };
     constexpr int HB = (WS == 16) ? 8 : XP;      // pixel 8 of the stage: 8 rows further in the same image row, or the start of the next one
     constexpr int NS = SPU * NUN, NM = 9 * NPR, S0 = NM / 3;
-    static_assert(NS <= NM - S0, "one slice per MFMA");
+    constexpr int SPM = (NS + (NM - S0) - 1) / (NM - S0);       // slices per MFMA behind the first third (one product: nine MFMAs per stage)
+    static_assert(NPL == 1 || SPM == 1, "one slice per MFMA");
     auto stage = [&](int cur, int nxt, auto conv_tag) {
         constexpr bool conv = decltype(conv_tag)::value;
         const uint8_t* st = lds + cur;
@@ -700,7 +724,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
         for (int pl = 0; pl < NPL; ++pl) af[pl] = frag(st + pl * PL_DY, ROW_DY, mfrag * 32, 8);
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) bf[0][pl] = frag(st + NPL * PL_DY + pl * PL_X, ROW_X, cbl * 32, HB);
-        constexpr int PA[6] = {NPL == 2 ? 1 : 2, 0, NPL == 2 ? 0 : 1, 1, 0, 0}, PB[6] = {0, NPL == 2 ? 1 : 2, NPL == 2 ? 0 : 1, 0, 1, 0};
+        constexpr int PA[6] = {NPL == 1 ? 0 : (NPL == 2 ? 1 : 2), 0, NPL == 2 ? 0 : 1, 1, 0, 0}, PB[6] = {0, NPL == 2 ? 1 : 2, NPL == 2 ? 0 : 1, 0, 1, 0};
         int n = 0, done = 0;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -713,10 +737,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
             for (int t = 0; t < NPR; ++t, ++n) {
                 acc[tap] = wg_mfma<NPL>(af[PA[t]], bf[tap & 1][PB[t]], acc[tap]);
                 if constexpr (conv) {
-                    // (n, hence upto and done, are compile-time values once the tap / product loops are unrolled; NS <= NM - S0:
-                    // at most one slice per MFMA - no inner loop over the slices, which the unroller gives up on at this size)
+                    // (n, hence upto and done, are compile-time values once the tap / product loops are unrolled.  NPL >= 2: NS <= NM - S0,
+                    // at most one slice per MFMA - no inner loop over all NS slices, which the unroller gives up on at this size.
+                    // NPL = 1: nine MFMAs per stage, so SPM = 2 or 3 slices behind each of the last six - a loop of that constant trip
+                    // count around the same one-slice statement unrolls like the statement itself, and the body is a third the size)
                     const int upto = (n + 1 <= S0) ? 0 : ((n + 1 - S0) * NS + (NM - S0) - 1) / (NM - S0);
-                    if (done < upto) { slice(nxt, done); ++done; }
+                    if constexpr (NPL == 1) {
+#pragma unroll
+                        for (int q = 0; q < SPM; ++q)
+                            if (done < upto) { slice(nxt, done); ++done; }
+                    } else {
+                        if (done < upto) { slice(nxt, done); ++done; }
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -745,7 +777,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_x6_kernel(const WgradArgs 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + mfrag * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            wsg[((int64_t)split * a.cout + co) * a.K + kcol] = NPL == 2 ? acc[tap][r] * dsc : acc[tap][r];
+            wsg[((int64_t)split * a.cout + co) * a.K + kcol] = NPL <= 2 ? acc[tap][r] * dsc : acc[tap][r];
         }
     }
 }
@@ -960,6 +992,7 @@ __global__ __launch_bounds__(256) void colsum_small_kernel(const float* x, int r
 
 int g_last_kernel = 0;
 int g_last_h2 = 0;
+int g_last_planes = 0;
 
 }  // namespace
 
@@ -967,6 +1000,8 @@ int g_last_h2 = 0;
 // 2 split-bf16 3x3 tap-sharing 64 x 2 chunks, 3 the same 128 x 1 chunk, 4 the small 1x1 kernel (one launch, fp32)
 extern "C" int egr_wgrad_last_kernel(void) { return g_last_kernel; }
 extern "C" int egr_wgrad_last_h2(void) { return g_last_h2; }
+// planes per operand of the last call's main launch: 1 one product, 2 the fp16 scheme, 3 the bf16 scheme (0: a fp32 kernel)
+extern "C" int egr_wgrad_last_planes(void) { return g_last_planes; }
 
 extern "C" int egr_conv2d_wgrad_ex_f32(const egr_conv_desc* dd, const float* x, const float* dy, float* dw, float* db, float* workspace,
                                        size_t workspace_floats, int32_t accumulate, const uint32_t* amax_x, const uint32_t* amax_dy, void* stream);
@@ -982,6 +1017,7 @@ extern "C" int egr_conv2d_wgrad_ex_f32(const egr_conv_desc* dd, const float* x, 
     if (!dd || !x || !dy || !dw || !workspace) return EGR_ENULL;
     if ((dd->w_format & EGR_W_F16X2) && (!amax_x || !amax_dy)) return EGR_ENULL;
     if ((dd->w_format & EGR_W_F16X2) && ((((uintptr_t)amax_x) | ((uintptr_t)amax_dy)) & 3)) return EGR_EINVAL;
+    if ((dd->w_format & EGR_W_F16X1) && !(dd->w_format & EGR_W_F16X2)) return EGR_EINVAL;      // (one product: of the fp16 scheme's operands)
     const egr_conv_desc& d = *dd;
     if (d.groups < 1 || d.groups > 65535 || d.transposed || d.out_nchw) return EGR_EINVAL;
     const int G = d.groups;
@@ -1030,6 +1066,7 @@ extern "C" int egr_conv2d_wgrad_ex_f32(const egr_conv_desc* dd, const float* x, 
             hipLaunchKernelGGL(wgrad_small_kernel, dim3((unsigned)tiles32, 1, (unsigned)G), dim3(64 * WSM_NW), 0, (hipStream_t)stream, a);
             g_last_kernel = 4;
             g_last_h2 = 0;
+            g_last_planes = 0;
             return egr_launch_status();
         }
     }
@@ -1080,7 +1117,17 @@ extern "C" int egr_conv2d_wgrad_ex_f32(const egr_conv_desc* dd, const float* x, 
     g_last_kernel = x6 ? (wg3 ? 1 + wg3 : 1) : 0;
     const bool h2 = x6 && (d.w_format & EGR_W_F16X2);        // the split launch in the fp16 scheme (two planes, three products)
     g_last_h2 = h2 ? 1 : 0;
-    if (h2 && wg3) {
+    const bool h1 = h2 && (d.w_format & EGR_W_F16X1);        // ... its high planes only, one product
+    g_last_planes = h1 ? 1 : (h2 ? 2 : (x6 ? 3 : 0));
+    if (h1 && wg3) {
+        if (wg3 == 2 && narrow) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<128, 1, 8, 1>), grid, dim3(256), 0, s, a);
+        else if (wg3 == 2) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<128, 1, 16, 1>), grid, dim3(256), 0, s, a);
+        else if (narrow) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<64, 2, 8, 1>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((conv_wgrad3_x6_kernel<64, 2, 16, 1>), grid, dim3(256), 0, s, a);
+    } else if (h1) {
+        if (bco == 128) hipLaunchKernelGGL((conv_wgrad_x6_kernel<128, 1>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((conv_wgrad_x6_kernel<64, 1>), grid, dim3(256), 0, s, a);
+    } else if (h2 && wg3) {
         if (wg3 == 2 && narrow) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<128, 1, 8, 2>), grid, dim3(256), 0, s, a);
         else if (wg3 == 2) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<128, 1, 16, 2>), grid, dim3(256), 0, s, a);
         else if (narrow) hipLaunchKernelGGL((conv_wgrad3_x6_kernel<64, 2, 8, 2>), grid, dim3(256), 0, s, a);

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
@@ -73,13 +73,19 @@ class LaunchPolicy:
     layer_h2: bool = True
     fused_layer: bool = True
     fused_query: bool = True
+    # the half-precision TRAINING arithmetic on top of w_format "f16" (fast_training(), opt-in: outside the parity contract): the training
+    # step's role-split conv launches and its split weight gradients multiply fp16-rounded operands with one product
+    train_one_product: bool = False
 
     @classmethod
     def from_env(cls, env=None) -> "LaunchPolicy":
         e = os.environ if env is None else env
         fmt = e.get("EGR_W_FORMAT", "f16x2")
         fp16 = fmt in ("f16x2", "f16")
-        return cls(w_format=fmt, h2=fp16,
+        tfmt = e.get("EGR_TRAIN_FORMAT", "")
+        if tfmt not in ("", "f16") or (tfmt == "f16" and fmt != "f16"):
+            raise ValueError("egorear_amd: EGR_TRAIN_FORMAT=f16 is the only value, and it requires EGR_W_FORMAT=f16")
+        return cls(train_one_product=tfmt == "f16", w_format=fmt, h2=fp16,
                    x6_min_rows=int(e.get("EGR_X6_MIN_ROWS", "4096")), x6_min_flops=float(e.get("EGR_X6_MIN_FLOPS", "5e8")),
                    x6_train_min_rows=int(e.get("EGR_X6_TRAIN_MIN_ROWS", "8192")), x6_train_min_flops=float(e.get("EGR_X6_TRAIN_MIN_FLOPS", "4e9")),
                    chain=e.get("EGR_CONV_CHAIN", "1") != "0", chain_min_rows=int(e.get("EGR_CONV_CHAIN_MIN_ROWS", "8192")),
@@ -93,7 +99,10 @@ class LaunchPolicy:
     def pack_key(self) -> tuple:
         """The fields that shape packed weights and abs-max arenas (engine.State, train.PackCache): packs made under one key are not
         valid under another."""
-        return (self.w_format, self.h2, self.layer_h2)
+        key = (self.w_format, self.h2, self.layer_h2)
+        # (the training mode adds an element instead of widening every key: a captured step replays the launches it recorded, one-product
+        # ones included, so a cache made under fast_training() is not fast()'s - and the keys of all other policies stay what they were)
+        return key + ("train_f16",) if self.train_one_product else key
 
     def exact(self) -> "LaunchPolicy":
         """The exact-operand arithmetic (EGR_W_FORMAT=bf16x3): three bf16 planes, six products, fused layers on the fp32 matrix cores."""
@@ -105,8 +114,18 @@ class LaunchPolicy:
         role-split conv kernel multiply the fp16 scheme's HIGH planes only - fp16-rounded operands, one matrix product instead of
         three, fp32 accumulation (EGR_W_F16X1).  Same packs and records as "f16x2" (made again under this policy's own
         pack_key); every launch without a one-product kernel - stem, chains, fused layers, weight stream, small launches - runs what
-        it runs under the default policy.  The training step ignores the bit: it computes what it computes under "f16x2"."""
+        it runs under the default policy.  The training step ignores the bit: it computes what it computes under "f16x2" (its own
+        half-precision mode is fast_training())."""
         return self.replace(w_format="f16", h2=True, layer_h2=True)
+
+    @_on_default
+    def fast_training(self) -> "LaunchPolicy":
+        """fast() plus the half-precision TRAINING arithmetic (EGR_W_FORMAT=f16 EGR_TRAIN_FORMAT=f16), opt-in and outside the parity
+        contract: the training step's role-split conv launches - statistics epilogue, masked and plain stride-1 data gradients
+        (EGR_W_F16X1T) - and its split weight gradients (EGR_W_F16X1 on egr_conv2d_wgrad_ex_f32) multiply the HIGH fp16 planes only,
+        one product, fp32 accumulation.  Master weights, optimizer, BatchNorm and every launch without a one-product
+        kernel are what they are under the default policy; no loss scaling (every operand is pre-scaled from its abs-max record)."""
+        return self.fast().replace(train_one_product=True)
 
     @property
     def fp16_scheme(self) -> bool:
@@ -161,7 +180,7 @@ EXPORTS = [
     "egr_preprocess_fused_u8_f32", "egr_preprocess_band_rows", "egr_conv_set_persist", "egr_stem_conv7x7_pool_f32",
     "egr_stem_w6_bytes", "egr_pack_stem_w6_f32", "egr_stem_conv7x7_x6_f32", "egr_wgrad_last_kernel", "egr_conv_last_kernel", "egr_conv_set_tap", "egr_conv_set_tapx", "egr_conv_set_splitk_fused", "egr_fisheye_project2_f32", "egr_pack_layer_w_f32", "egr_pack_layer_wh2_f32",
     "egr_conv2d_nhwc_ex_f32", "egr_wh2_elems", "egr_pack_wh2_f32", "egr_absmax_f32", "egr_stem_conv7x7_x6_ex_f32", "egr_stem_wh2_bytes", "egr_pack_stem_wh2_f32", "egr_stem_conv7x7_h2_f32",
-    "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2",
+    "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2", "egr_wgrad_last_planes",
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
     "egr_conv_plan",
@@ -201,7 +220,7 @@ class ConvPlan(C.Structure):
 # egr_conv_route: the values of ConvPlan.route and of conv_last_kernel()
 ROUTE_F32_TILED, ROUTE_SPLIT_TILED, ROUTE_TAP, ROUTE_TAP2, ROUTE_STREAM_1X1, ROUTE_SMALL_F32, ROUTE_TAPX = range(7)
 # egr_conv_desc.w_format bits the wrappers set by name (include/egorear_hip.h)
-W_F16X2, W_F16X1 = 4, 8
+W_F16X2, W_F16X1, W_F16X1T = 4, 8, 16
 
 
 class ChainAux(C.Structure):
@@ -259,6 +278,7 @@ def _load() -> C.CDLL:
     lib.egr_stem_conv7x7_f32.argtypes = [vp, NMap, i32, i32, i32, vp, vp, vp, vp, i32, i64, vp]
     lib.egr_stem_conv7x7_pool_f32.argtypes = [vp, NMap, i32, i32, i32, vp, vp, vp, vp, i32, i64, vp]
     lib.egr_wgrad_last_kernel.argtypes = []
+    lib.egr_wgrad_last_planes.argtypes = []
     lib.egr_conv_last_kernel.argtypes = []
     lib.egr_conv_set_tap.argtypes = [i32]
     lib.egr_conv_set_tapx.argtypes = [i32, i32, i32]
@@ -351,7 +371,7 @@ def _check(rc: int, name: str):
 # When PROFILE is a list, every launch is bracketed by HIP events recorded on the launch stream (torch's current
 # stream) and (kernel name, start, end, algorithmic work) is appended; bench.py uses this for the roofline leg.
 PROFILE = None
-# When PLAN_LOG is a list, every forward conv2d launch first asks egr_conv_plan what it is about to launch and appends
+# When PLAN_LOG is a list, every conv2d launch (the masked data gradients too) first asks egr_conv_plan what it is about to launch and appends
 # (tag, ConvPlan): which launches of a forward took which route / variant / plane count (tests, tools/fast_bench.py).
 PLAN_LOG = None
 
@@ -645,13 +665,16 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
            split_k: int = 1, groups: int = 1, gx: Optional[int] = None, gy: Optional[int] = None,
            gr: Optional[int] = None, grs: int = 0, grm: int = 0, transposed_out_hw: Optional[tuple] = None, x6_min: Optional[tuple] = None,
            mask: Optional[Img] = None, amax_out: Optional[torch.Tensor] = None, amax_arena: Optional["AmaxArena"] = None,
-           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None, one_product: Optional[bool] = None) -> Optional[Img]:
+           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None, one_product: Union[bool, str, None] = None) -> Optional[Img]:
     """Implicit-GEMM conv / linear.  Output goes to `out` (NHWC Img, maybe a channel slice), or to the raw
     tensor `out_nchw` (channel-major planes placed by `ymap`), or to a fresh NHWC tensor.
 
     groups > 1: `groups` same-shape problems in one launch.  w is (groups, cout_pad, K), scale/shift
     (groups, cout_pad).  x / out / res hold the images of all groups back to back (group stride = images per group x
-    image stride) unless an explicit element stride gx / gy / gr is given, in which case they describe group 0."""
+    image stride) unless an explicit element stride gx / gy / gr is given, in which case they describe group 0.
+
+    one_product: None = the policy's forward rule (w_format "f16"), True / False = EGR_W_F16X1 on / off (tests), "train" = the training
+    step under LaunchPolicy.train_one_product: EGR_W_F16X1 | EGR_W_F16X1T, the role-split route's training launches take one product too."""
     pol = policy()
     x_full = x.t
     if groups > 1:
@@ -704,8 +727,9 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     # the fast policy (or one_product=True: tests): the same operands plus EGR_W_F16X1 - the dispatch takes a one-product kernel where
     # one exists (plan.planes == 1) and treats the bit as absent everywhere else
     h1 = h2 and (pol.w_format == "f16" if one_product is None else bool(one_product))
+    h1t = h1 and one_product == "train"
     if h1:
-        d.w_format |= W_F16X1
+        d.w_format |= W_F16X1 | (W_F16X1T if h1t else 0)
     d.n, d.h, d.w, d.cin, d.cout = x.n, x.h, x.w, x.c, cout
     d.kh, d.kw, d.stride, d.pad, d.ho, d.wo = kh, kw, stride, pad, ho, wo
     d.ldx = x.ld
@@ -769,11 +793,20 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
                           _p(amax_out, torch.int32).value if amax_out is not None else None)
         ret.tag(amax_out)
         x6 = x6 and not h2     # (the tag below)
+        fmt = "h2 " if h2 else ""
+        if PLAN_LOG is not None or (h1t and PROFILE is not None):
+            dev, plan = _DEV[0], ConvPlan()
+            _check(lib.egr_conv_plan(C.byref(d), _p(x.t), wptr, None, None, _p(res.t) if res is not None else None, None, None, _p(mask.t),
+                                     yptr, ws_ptr, ws_n, C.byref(aux) if aux is not None else None, C.byref(plan)), "egr_conv_plan")
+            _DEV[0] = dev
+            fmt = "h1 " if plan.planes == 1 else fmt       # (the tag says what the launch multiplies)
+            if PLAN_LOG is not None:
+                PLAN_LOG.append((f"{fmt}masked G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}", plan))
         _launch("egr_conv2d_nhwc_f32", lib.egr_conv2d_masked_ex_f32, C.byref(d), _p(x.t), wptr, _p(res.t) if res is not None else None,
                 _p(mask.t), yptr, ws_ptr, ws_n, C.byref(aux) if aux is not None else None, _stream(),
                 flops=2.0 * M * cout * K * groups / (stride * stride if transposed_out_hw is not None else 1),
                 nbytes=4.0 * groups * (2 * M * cout + x.n * x.h * x.w * x.c + cout * K),
-                tag=f"{'T ' if transposed_out_hw is not None else ''}{'h2 ' if h2 else ''}{'x6 ' if x6 else ''}masked G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}" if PROFILE is not None else "")
+                tag=f"{'T ' if transposed_out_hw is not None else ''}{fmt}{'x6 ' if x6 else ''}masked G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}" if PROFILE is not None else "")
         return ret
     if out_nchw is not None:
         amax_out = None          # (the channel-major epilogue keeps no record)
@@ -794,13 +827,16 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
             aux.bn_tiles_out = C.addressof(tiles)
             aux.bn_capacity = bn_ws.numel()
     fmt = ("h1 " if h1 else "h2 ") if h2 else ("x6 " if x6 else "")
-    if PLAN_LOG is not None:
+    if PLAN_LOG is not None or (h1t and PROFILE is not None):
         dev, plan = _DEV[0], ConvPlan()
         _check(lib.egr_conv_plan(C.byref(d), _p(x.t), wptr, _p(scale), _p(shift), _p(res.t) if res is not None else None, _p(rowscale),
                                  _p(rowmask, torch.uint8), None, yptr, ws_ptr, ws_n, C.byref(aux) if aux is not None else None, C.byref(plan)),
                "egr_conv_plan")
         _DEV[0] = dev
-        PLAN_LOG.append((f"{fmt}G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}", plan))
+        if h1t:                                        # the training step: the tag says what the launch multiplies
+            fmt = "h1 " if plan.planes == 1 else "h2 "
+        if PLAN_LOG is not None:
+            PLAN_LOG.append((f"{fmt}G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}", plan))
     _launch("egr_conv2d_nhwc_f32", lib.egr_conv2d_nhwc_ex_f32, C.byref(d), _p(x.t), wptr, _p(scale), _p(shift),
             _p(res.t) if res is not None else None, _p(rowscale), _p(rowmask, torch.uint8), yptr, ws_ptr, ws_n,
             C.byref(aux) if aux is not None else None, _stream(),
@@ -908,10 +944,12 @@ def wgrad_records(x: Img, dy: Img, amax_arena: Optional["AmaxArena"]) -> None:
 
 def conv2d_wgrad(x: Img, dy: Img, kh: int, kw: int, stride: int, pad: int, workspace: torch.Tensor, *, want_bias: bool = False,
                  dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None, accumulate: bool = False, groups: int = 1,
-                 x6: Optional[bool] = None, amax_arena: Optional["AmaxArena"] = None, gx: Optional[int] = None, gy: Optional[int] = None):
+                 x6: Optional[bool] = None, amax_arena: Optional["AmaxArena"] = None, gx: Optional[int] = None, gy: Optional[int] = None,
+                 one_product: Optional[bool] = None):
     """Weight (+ bias) gradient of the forward conv x -> y.  x, dy NHWC Imgs (all groups' images back to back when
     groups > 1).  Returns (dw, db): dw ([groups,] cout, kh*kw*cin) in the packed K order of conv2d
-    (engine.unpack_conv_weight turns it back into OIHW), db ([groups,] cout)."""
+    (engine.unpack_conv_weight turns it back into OIHW), db ([groups,] cout).
+    one_product (None: LaunchPolicy.train_one_product): a split launch in the fp16 scheme multiplies the high planes only (EGR_W_F16X1)."""
     cin, cout = x.c, dy.c
     interleaved = gx is not None or gy is not None      # groups = channel slices of ONE batch (x, dy: group 0's slice; gx / gy: element strides)
     if interleaved and (gx is None or gy is None):
@@ -937,8 +975,9 @@ def conv2d_wgrad(x: Img, dy: Img, kh: int, kw: int, stride: int, pad: int, works
     if split:
         wgrad_records(x, dy, amax_arena)
     h2 = split and policy().h2 and x.amax is not None and dy.amax is not None
+    h1 = h2 and (policy().train_one_product if one_product is None else bool(one_product))
     if h2:
-        d.w_format |= 4
+        d.w_format |= W_F16X2 | (W_F16X1 if h1 else 0)
     shape_w, shape_b = ((groups, cout, K), (groups, cout)) if groups > 1 else ((cout, K), (cout,))
     if dw is None:
         dw = torch.empty(shape_w, device=x.t.device, dtype=torch.float32)
@@ -949,7 +988,7 @@ def conv2d_wgrad(x: Img, dy: Img, kh: int, kw: int, stride: int, pad: int, works
     _launch("egr_conv2d_wgrad_f32", lib.egr_conv2d_wgrad_ex_f32, C.byref(d), _p(x.t), _p(dy.t), _p(_cont(dw, "dw")), _p(db),
             _p(workspace), workspace.numel(), 1 if accumulate else 0, _p(x.amax, torch.int32) if h2 else None,
             _p(dy.amax, torch.int32) if h2 else None, _stream(), flops=2.0 * dy.n * dy.h * dy.w * cout * K,
-            tag=f"{'h2 ' if h2 else ''}G{groups} M{ng * dy.h * dy.w} N{cout} K{K} k{kh}s{stride} cin{cin}" if PROFILE is not None else "")
+            tag=f"{('h1 ' if h1 else 'h2 ') if h2 else ''}G{groups} M{ng * dy.h * dy.w} N{cout} K{K} k{kh}s{stride} cin{cin}" if PROFILE is not None else "")
     return dw, db
 
 

@@ -45,8 +45,11 @@ OVERLAP = True          # the leaves of the reverse pass on a second stream (Ste
 
 def _conv2d(*a, **k):
     """hip.conv2d under the training step's split-launch rule (hip.X6_TRAIN_MIN_*).  The step keeps its own arithmetic: under the fast
-    policy (hip.LaunchPolicy.fast) it ignores the one-product bit and computes what it computes under "f16x2"."""
-    return hip.conv2d(*a, x6_min=(hip.policy().x6_train_min_rows, hip.policy().x6_train_min_flops), one_product=False, **k)
+    policy (hip.LaunchPolicy.fast) it ignores the one-product bit and computes what it computes under "f16x2".  Its own half-precision
+    mode is LaunchPolicy.fast_training() (train_one_product; DESIGN.md 5l, outside the parity contract): the role-split route's
+    training launches then take their one-product forms, every other launch is unchanged."""
+    return hip.conv2d(*a, x6_min=(hip.policy().x6_train_min_rows, hip.policy().x6_train_min_flops),
+                      one_product="train" if hip.policy().train_one_product else False, **k)
 
 
 def _ceil32(n: int) -> int:

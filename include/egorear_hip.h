@@ -96,7 +96,12 @@ enum { EGR_W_F32 = 0, EGR_W_BF16X3 = 1,
         * §5k).  w is the same F16X2 image; where a one-product kernel exists - the forward launches of the role-split route - both
         * operands are multiplied as their HIGH planes only, f16(x 2^e) f16(w 2^k), one matrix product instead of three: fp16-rounded
         * operands (relative 2^-11 each), fp32 accumulation.  Every other launch treats the bit as absent. */
-       EGR_W_F16X1 = 8 };
+       EGR_W_F16X1 = 8,
+       /* With EGR_W_F16X2 | EGR_W_F16X1 only (EGR_EINVAL otherwise): the half-precision TRAINING policy.  The training
+        * launches of the role-split route - statistics epilogue, masked and plain stride-1 data gradients - take their one-product form
+        * too.  Every other launch treats the bit as absent.  egr_conv2d_wgrad_ex_f32 does not read it: there EGR_W_F16X1 beside
+        * EGR_W_BF16X3 | EGR_W_F16X2 asks for the one-product split kernels. */
+       EGR_W_F16X1T = 16 };
 
 /* Split a packed fp32 weight matrix w (groups, npad, k) — npad = round_up(cout, 32), k = kh*kw*cin, k % 32 == 0 — into
  * the EGR_W_BF16X3 image: per group egr_w6_elems(npad, k) bf16 elements laid out
@@ -235,11 +240,11 @@ typedef struct {
      *                            1 residual / 2 residual upsampled on the fly)
      *   TAPX                     100 T + 10 R + cfg  (T 0 forward / 1 statistics epilogue / 2 masked data gradient, R 1 with residual,
      *                            cfg = the kernel's (tile, wave tile, stride) configuration 0, 1, 3 .. 7); + 1000: the one-product
-     *                            form of a forward variant (EGR_W_F16X1)
+     *                            form of a forward variant (EGR_W_F16X1) or of a training / data-gradient one (EGR_W_F16X1T)
      *   others                   0 */
     int32_t variant;
     int32_t planes;              /* 16-bit planes multiplied per operand: 2 (EGR_W_F16X2), 3 (EGR_W_BF16X3), 0 (fp32); 1: a one-product
-                                  * launch (EGR_W_F16X1 on a TAPX forward variant) */
+                                  * launch (EGR_W_F16X1 on a TAPX forward variant, EGR_W_F16X1T on the others) */
     int32_t tiles_m, tiles_n;    /* tiles per group */
     int32_t grid_x, grid_y, grid_z, block;     /* the main launch */
     int32_t split_k, ktiles_per_split;        /* K slices (1: none) of ktiles_per_split 32-deep chunks, none empty */
@@ -269,11 +274,17 @@ int egr_conv2d_wgrad_f32(const egr_conv_desc* d, const float* x, const float* dy
 /* ... in the fp16 scheme when d->w_format carries EGR_W_F16X2 beside EGR_W_BF16X3 [| EGR_W_FORCE]: the split launches
  * then take both operands as two fp16 planes of the value times a power of two from its abs-max record (amax_x / amax_dy: 64 slots
  * each, as egr_conv_aux.amax_in) - three matrix products per fp32 product instead of six; the accumulators are scaled back when the
- * partial tiles are written.  Launches below the split threshold ignore the records (fp32 matrix cores). */
+ * partial tiles are written.  Launches below the split threshold ignore the records (fp32 matrix cores).
+ * EGR_W_F16X1 on top of that (EGR_EINVAL without EGR_W_F16X2): the split launches stage the HIGH plane of both operands only,
+ * f16(dy 2^e) f16(x 2^k), and issue ONE product (outside the parity contract).  Same records, same slabs and split
+ * count, same bias gradient (a sum of fp32 dy: bit-identical to the three-product launch's). */
 int egr_conv2d_wgrad_ex_f32(const egr_conv_desc* d, const float* x, const float* dy, float* dw, float* db, float* workspace,
                             size_t workspace_floats, int32_t accumulate, const uint32_t* amax_x, const uint32_t* amax_dy, void* stream);
 /* diagnostic (tests): 1 when the last weight-gradient call launched a fp16-scheme kernel */
 int egr_wgrad_last_h2(void);
+/* diagnostic (tests): 16-bit planes per operand of the last weight-gradient call's main launch - 1 (EGR_W_F16X1), 2 (fp16 scheme), 3 (bf16
+ * scheme); 0: a fp32 kernel */
+int egr_wgrad_last_planes(void);
 /* diagnostic (tests): the kernel the last egr_conv2d_wgrad_f32 call launched - 0 fp32 MFMA, 1 split-bf16 generic,
  * 2 / 3 split-bf16 3x3 stride-1 tap-sharing (64 channels x 2 input chunks / 128 x 1), 4 the small 1x1 kernel (fp32 path, 1x1 / stride 1,
  * rows x groups <= 8192, at most 256 tiles of 32 x 32: weight and bias gradient in ONE launch, no slabs; env EGR_WGRAD_SMALL=0

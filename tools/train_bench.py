@@ -2,6 +2,7 @@
 
     python tools/train_bench.py [--batch 32] [--steps 5]
     python tools/train_bench.py --graph --accumulate 8      # gradient accumulation: ms per micro-step and per optimizer update
+    python tools/train_bench.py --graph --policy fast_training     # the half-precision training policy (tags say h1)
 """
 import argparse
 import collections
@@ -28,7 +29,14 @@ def main():
     ap.add_argument("--dump", default="", help="write every launch of the instrumented step (order, us, name, tag) to this file")
     ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer update (--steps / --warmup then count updates)")
     ap.add_argument("--json", default="", help="with --accumulate: also write the figures to this file")
+    ap.add_argument("--policy", choices=["default", "fast_training"], default="default",
+                    help="launch policy of the step: the process default, or hip.LaunchPolicy.fast_training() (outside the parity contract)")
     a = ap.parse_args()
+    with hip.use_policy(hip.LaunchPolicy.fast_training() if a.policy == "fast_training" else None):
+        run(a)
+
+
+def run(a):
     dev = "cuda:0"
     net = EgoPoseFormerMVFEX(**copy.deepcopy(configs.pose3d_cfg("ego4view_rw")))
     synth.load_synth(net, 42)
@@ -53,7 +61,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     print(f"host enqueue time {host / a.steps * 1e3:.2f} ms/step")
-    print(f"batch {B}: {dt * 1e3:.2f} ms/step, {B / dt:.1f} frames/s, loss {float(terms.sum()):.4f}, mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    print(f"policy {a.policy}, batch {B}: {dt * 1e3:.2f} ms/step, {B / dt:.1f} frames/s, loss {float(terms.sum()):.4f}, mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
     # per-kernel breakdown of one step
     # eager and instrumented even when the timed steps were graph replays - and on ONE stream: with the two-stream reverse pass a
     # launch's event pair would also time whatever the other stream runs beside it
