@@ -183,7 +183,7 @@ EXPORTS = [
     "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2", "egr_wgrad_last_planes",
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
-    "egr_conv_plan",
+    "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
 ]
 
 
@@ -302,6 +302,9 @@ def _load() -> C.CDLL:
     lib.egr_upsample2x_nhwc_f32.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.egr_avgpool_nhwc_f32.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.egr_argmax_rows_f32.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+    lib.egr_soft_argmax_f32.argtypes = [vp, i32, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
+    lib.egr_soft_argmax_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp, vp]
+    lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
     lib.egr_msda_gather_f32.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]
@@ -1195,6 +1198,71 @@ def argmax_rows(hm: torch.Tensor, thr: float):
     _launch("egr_argmax_rows_f32", lib.egr_argmax_rows_f32, _p(hm), rows, H, W, float(thr), _p(anchors), _p(maxvals), _p(valid, torch.uint8),
                                    _p(index, torch.int32), _stream(), nbytes=4.0 * hm.numel() + 17.0 * rows)
     return anchors, maxvals, valid, index
+
+
+def _maps(hm: torch.Tensor, what: str):
+    """(rows, H, W) of a contiguous (..., H, W) tensor of heat maps."""
+    if hm.dim() < 2:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (..., H, W), got {tuple(hm.shape)}")
+    _cont(hm, "heatmap")
+    H, W = hm.shape[-2:]
+    if H * W == 0 or hm.numel() == 0:
+        raise ValueError(f"egorear_amd.{what}: empty heat maps {tuple(hm.shape)}")
+    return hm.numel() // (H * W), H, W
+
+
+def soft_argmax(hm: torch.Tensor, beta: float = 1.0, mode: int = 0, normalize: bool = False, thr: float = 0.0, want_probs: bool = False):
+    """hm (..., H, W) contiguous -> coords (rows,2) f32 (x, y), maxvals (rows,), index (rows,) i32, valid (rows,) u8, stat (rows,2) f32,
+    probs (rows,H,W) | None: egr_soft_argmax_f32, one read of the maps for the soft and the hard decode (mode 0 softmax, 1 relu mass)."""
+    rows, H, W = _maps(hm, "soft_argmax")
+    dev = hm.device
+    coords = torch.empty((rows, 2), device=dev, dtype=torch.float32)
+    maxvals = torch.empty((rows,), device=dev, dtype=torch.float32)
+    index = torch.empty((rows,), device=dev, dtype=torch.int32)
+    valid = torch.empty((rows,), device=dev, dtype=torch.uint8)
+    stat = torch.empty((rows, 2), device=dev, dtype=torch.float32)
+    probs = torch.empty((rows, H, W), device=dev, dtype=torch.float32) if want_probs else None
+    _launch("egr_soft_argmax_f32", lib.egr_soft_argmax_f32, _p(hm), rows, H, W, float(beta), int(mode), 1 if normalize else 0, float(thr),
+            _p(coords), _p(maxvals), _p(index, torch.int32), _p(valid, torch.uint8), _p(stat), _p(probs), _stream(),
+            nbytes=4.0 * hm.numel() * (2 if want_probs else 1) + 25.0 * rows)
+    return coords, maxvals, index, valid, stat, probs
+
+
+def soft_argmax_bwd(hm: torch.Tensor, stat: torch.Tensor, coords: torch.Tensor, index: torch.Tensor, g_coords: torch.Tensor,
+                    g_maxvals: Optional[torch.Tensor] = None, beta: float = 1.0, mode: int = 0, normalize: bool = False,
+                    out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """Gradient of soft_argmax with respect to hm, from the forward's stat / coords / index: egr_soft_argmax_bwd_f32.  `out` (shaped like
+    hm) is overwritten, or added to with accumulate=True; without `out` a new tensor is returned."""
+    rows, H, W = _maps(hm, "soft_argmax_bwd")
+    for t, n, what in ((stat, 2 * rows, "stat"), (coords, 2 * rows, "coords"), (index, rows, "index"), (g_coords, 2 * rows, "g_coords"),
+                       (g_maxvals, rows, "g_maxvals")):
+        if t is not None and (t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"egorear_amd.soft_argmax_bwd: {what} must be contiguous with {n} elements, got {tuple(t.shape)}")
+    if out is None:
+        if accumulate:
+            raise ValueError("egorear_amd.soft_argmax_bwd: accumulate needs `out`")
+        out = torch.empty_like(hm)
+    elif out.shape != hm.shape or not out.is_contiguous():
+        raise ValueError("egorear_amd.soft_argmax_bwd: `out` must be contiguous and shaped like the heat maps")
+    _launch("egr_soft_argmax_bwd_f32", lib.egr_soft_argmax_bwd_f32, _p(hm), _p(stat), _p(coords), _p(index, torch.int32), _p(g_coords),
+            _p(g_maxvals), rows, H, W, float(beta), int(mode), 1 if normalize else 0, 1 if accumulate else 0, _p(out), _stream(),
+            nbytes=4.0 * hm.numel() * (3 if accumulate else 2) + 36.0 * rows)
+    return out
+
+
+def coord_l1(coords: torch.Tensor, index: torch.Tensor, valid: torch.Tensor, wid: int, weight: float, loss: torch.Tensor,
+             want_grad: bool = True) -> Optional[torch.Tensor]:
+    """loss (one device float64, overwritten) = weight * mean over valid maps of |x^ - x*| + |y^ - y*| with (x*, y*) = (index % wid,
+    index // wid); returns g_coords (rows,2) = weight * sign / N_valid (zero where invalid) | None: egr_coord_l1_f32."""
+    if loss.dtype != torch.float64 or loss.numel() != 1:
+        raise ValueError("egorear_amd.coord_l1: loss must be one float64")
+    rows = index.numel()
+    if rows == 0 or coords.numel() != 2 * rows or valid.numel() != rows or not (coords.is_contiguous() and index.is_contiguous() and valid.is_contiguous()):
+        raise ValueError("egorear_amd.coord_l1: coords (rows,2), index (rows,) and valid (rows,) must be contiguous and agree")
+    g = torch.empty((rows, 2), device=coords.device, dtype=torch.float32) if want_grad else None
+    _launch("egr_coord_l1_f32", lib.egr_coord_l1_f32, _p(coords), _p(index, torch.int32), _p(valid, torch.uint8), rows, int(wid), float(weight),
+            _p(loss, torch.float64), _p(g), _stream(), nbytes=(13.0 + (8.0 if want_grad else 0.0)) * rows)
+    return g
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

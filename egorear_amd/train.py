@@ -2018,10 +2018,20 @@ class HeatmapTrainer(Trainer):
     sum over views of w_heatmap * nn.MSELoss(mean) - per heat-map set in stage 2 (heatmap_loss_0 = initial, heatmap_loss_1 = refined) -
     backward, gradient-norm clip (trainer.gradient_clip_val 5.0) and ONE AdamW group over all parameters (lr 1e-3, weight decay
     5e-3, the warm-up hook of the wrappers).  Graph replay, the bucketed all-reduce and the BatchNorm buffer broadcast are the
-    Trainer's."""
+    Trainer's.
+
+    w_coord > 0 (opt-in; 0.0 launches nothing new) adds a coordinate loss through a soft-argmax to every heat-map set - the companion of
+    heat-map regression that the reference's JointsCoordinateLoss (utils/loss.py:180-200) was written for: w_coord * mean over the valid
+    joints of |x^ - x*| + |y^ - y*| in heat-map pixels, (x^, y^) the softmax-weighted mean position of the predicted map at `coord_beta`
+    (egr_soft_argmax_f32, mode 0), (x*, y*) the ground-truth map's first maximum, a joint valid where max(gt) >= coord_threshold (the rule
+    and default of metrics.heatmap_metrics).  Its dense gradient (egr_soft_argmax_bwd_f32) enters the tape next to the MSE term's, and
+    `step` returns one coordinate term per set behind the MSE terms: (2,) in stage 1, (4,) in stage 2.  The mean is over THIS rank's (and
+    this micro-batch's) valid joints: under a process group or with accumulate > 1 the optimised quantity is a mean of per-rank means,
+    which differs from the mean over all valid joints when the ranks see different numbers of them."""
 
     def __init__(self, net: nn.Module, lr: float = 1e-3, weight_decay: float = 5e-3, clip: float = 5.0, warmup_iters: int = 500,
-                 w_heatmap: float = 10.0, process_group=None, use_graph: bool = False, accumulate: int = 1):
+                 w_heatmap: float = 10.0, process_group=None, use_graph: bool = False, accumulate: int = 1, w_coord: float = 0.0,
+                 coord_beta: float = 100.0, coord_threshold: float = 1.0):
         from .estimator import EgoPoseFormerHeatmap, EgoPoseFormerHeatmapMVFEX
         if isinstance(net, EgoPoseFormerHeatmapMVFEX):
             self.kind = "mvfex"
@@ -2032,6 +2042,9 @@ class HeatmapTrainer(Trainer):
         self.net = net
         self.opt = FusedAdamW(net, lr, weight_decay, clip, warmup_iters, process_group=process_group, decay_all=True, accumulate=accumulate)
         self.w_mpjpe, self.w_heatmap = 0.0, w_heatmap
+        if not (w_coord >= 0.0 and coord_beta > 0.0 and math.isfinite(w_coord) and math.isfinite(coord_beta)):
+            raise ValueError(f"egorear_amd.train.HeatmapTrainer: w_coord must be >= 0 and coord_beta > 0, got {w_coord!r}, {coord_beta!r}")
+        self.w_coord, self.coord_beta, self.coord_threshold = float(w_coord), float(coord_beta), float(coord_threshold)
         self.use_graph = use_graph
         self.graph = None
         self._eager_done = 0
@@ -2055,11 +2068,16 @@ class HeatmapTrainer(Trainer):
                 hms, feat_all, feat_ref = mvfex_heatmap_forward_train(S, net, img)
                 outs = (hms, feat_all, feat_ref)
             gt = gt_heatmap.to(device=S.dev, dtype=torch.float32).contiguous()
-            terms = torch.zeros(len(hms), dtype=torch.float64, device=S.dev)
+            terms = torch.zeros(len(hms) * (2 if self.w_coord > 0.0 else 1), dtype=torch.float64, device=S.dev)
             for i, h in enumerate(hms):      # sum over views of the per-view mean == V * the mean over everything (equal-sized views)
                 V = h.shape[1]               # (the stage-1 model sees one stereo pair: views [0, V) of the ground truth)
                 g = gt if gt.shape[1] == V else gt[:, :V].contiguous()
                 S.G.add(h, T.mse_loss(h, g, self.w_heatmap * V * scale, terms[i:i + 1]))
+                if self.w_coord > 0.0:       # the coordinate term: four launches, no host synchronisation
+                    _, _, gvalid, gidx = hip.argmax_rows(g, self.coord_threshold)
+                    coords, _, idx, _, stat, _ = hip.soft_argmax(h, self.coord_beta, 0, False, 0.0)
+                    gc = hip.coord_l1(coords, gidx, gvalid, h.shape[-1], self.w_coord * scale, terms[len(hms) + i:len(hms) + i + 1])
+                    S.G.add(h, hip.soft_argmax_bwd(h, stat, coords, idx, gc, None, self.coord_beta, 0, False))
             S.loss_terms = terms if scale == 1.0 else terms / scale
             self._close(S, update)
         return S, outs

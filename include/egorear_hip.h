@@ -431,6 +431,35 @@ int egr_avgpool_nhwc_f32(const float* x, float* y, int32_t n, int32_t hw, int32_
 int egr_argmax_rows_f32(const float* hm, int32_t rows, int32_t hgt, int32_t wid, float thr,
                         float* anchors /* rows x 2 */, float* maxvals, uint8_t* valid, int32_t* index, void* stream);
 
+/* Soft-argmax decoding of heat maps, replaces get_max_preds_soft_pytorch (utils/loss.py:145-177; beta 1, normalize) and
+ * integrate_tensor_2d (utils/util.py:80-109; beta = multiplier, mode 0 = softmax=True, mode 1 = softmax=False) - and, from the same
+ * single read of the map, the hard decode of get_max_preds (utils/loss.py:122-142).  hm: `rows` dense maps (hgt, wid) fp32; z = beta*h.
+ *   mode 0: p = softmax(z) over the map; mode 1: p = relu(z) / sum relu(z) (a map without positive mass gives NaN, like the 0/0 there);
+ *   coords (rows, 2) = (sum p*col, sum p*row), divided by (wid, hgt) when `normalize`; maxvals = max h, index = its first flat index
+ *   (the tie rule of egr_argmax_rows_f32), valid = [maxvals >= thr]; stat (rows, 2) = (max z, sum exp(z - max z) | sum relu(z)) for the
+ *   backward; probs (rows, hgt, wid) or NULL: softmax(z) in mode 0, relu(z) un-normalised in mode 1 (util.py:89, 109).
+ * One wave per map, fixed-order reductions, no atomics: a map's bits do not depend on the batch around it.  exp never sees a positive
+ * argument, so no beta * peak overflows.  Maps with hgt*wid <= 4096, hgt*wid % 4 == 0, wid >= 4 and 16-byte aligned tensors are read
+ * once into registers; every other shape below 2^24 elements takes scalar loads and reads the map twice.  EGR_EINVAL: beta not a
+ * positive finite number, mode outside 0..1, hgt*wid >= 2^24. */
+int egr_soft_argmax_f32(const float* hm, int32_t rows, int32_t hgt, int32_t wid, float beta, int32_t mode, int32_t normalize, float thr,
+                        float* coords /* rows x 2 */, float* maxvals, int32_t* index, uint8_t* valid, float* stat /* rows x 2 */,
+                        float* probs /* nullable */, void* stream);
+/* Backward of the above (what autograd makes of utils/util.py:80-109 / utils/loss.py:145-177), from the forward's hm, stat, coords and
+ * index:  g_hm[i] = beta p_i ((col_i - x) gx + (row_i - y) gy), p_i recomputed; (gx, gy) = g_coords, divided by (wid, hgt) when
+ * `normalize`; mode 1: beta [z_i > 0] (...) / sum relu(z), and zeros for a map without positive mass (the reference's autograd gives
+ * NaN there).  g_maxvals (rows) or NULL is added at `index`.  accumulate != 0 adds into g_hm.  Every element is written by one lane:
+ * the same bits every run. */
+int egr_soft_argmax_bwd_f32(const float* hm, const float* stat, const float* coords, const int32_t* index, const float* g_coords,
+                            const float* g_maxvals /* nullable */, int32_t rows, int32_t hgt, int32_t wid, float beta, int32_t mode,
+                            int32_t normalize, int32_t accumulate, float* g_hm, void* stream);
+/* Coordinate L1 loss on soft-argmax joints (the role of JointsCoordinateLoss, utils/loss.py:180-200, with an L1 distance in heat-map
+ * pixels): coords (rows, 2) predictions, (index, valid) the target maps' hard decode (egr_argmax_rows_f32), target = (index % wid,
+ * index / wid).  loss[0] = weight / max(N_valid, 1) * sum over valid maps of |x^ - x*| + |y^ - y*| (one fp64, overwritten);
+ * g_coords (rows, 2) or NULL = weight * sign(.) / max(N_valid, 1), zero where invalid.  One workgroup, fp64 sums in a fixed order. */
+int egr_coord_l1_f32(const float* coords, const int32_t* index, const uint8_t* valid, int32_t rows, int32_t wid, float weight,
+                     double* loss, float* g_coords /* nullable */, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
