@@ -9,11 +9,17 @@ that returns the soft and the hard decode of (B, V, J, H, W) maps from ONE launc
 The kernels are wrapped as `torch.library` operators (`egorear_amd::soft_argmax`, `egorear_amd::soft_argmax_bwd`) with fake
 implementations and a registered autograd formula, like `egorear_amd::msda_fwd`: gradient flows to the heat maps from the coordinates
 and from `maxvals`; `index`, `valid` and the probabilities are not differentiable.  There is no CPU path: CPU tensors raise.
+
+`triangulate_joints` takes the decoded joints of 2 to 4 calibrated fisheye views to one 3-D point per joint (cm, device frame) on
+`egr_triangulate_f32` / `egr_triangulate_bwd_f32` (DESIGN.md 5n) - operators `egorear_amd::triangulate`, `egorear_amd::triangulate_bwd`,
+differentiable in the point and the cost with respect to the coordinates and the confidences - and `decode_joints_3d` chains the two
+launches: heat maps -> Joints2D -> Joints3D, with no torch arithmetic in between.
 """
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Optional, Tuple
+import os
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -144,3 +150,171 @@ def decode_joints_2d(heatmaps: torch.Tensor, beta: float = 100.0, threshold: flo
     soft, maxvals, index, valid, _, _ = soft_argmax_op(heatmaps, float(beta), MODE_SOFTMAX, False, float(threshold), False)
     hard = torch.stack((index % W, torch.div(index, W, rounding_mode="floor")), -1).to(torch.float32)
     return Joints2D(soft, hard, maxvals, valid.view(torch.bool))     # (0 / 1 bytes: a reinterpretation, not a copy)
+
+
+# ---- triangulation ----------------------------------------------------------------------------------------------------------------
+
+_CAMERA_NAMES = ("camera_front_left", "camera_front_right", "camera_back_left", "camera_back_right")
+_PKG_CALIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "calib", "ego4view")
+_RAY_RECORDS = {}    # (camera_model, calibration directory | the cameras' ids, device) -> (cameras, (V, 30) device tensor)
+
+
+def _check_tri(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
+               min_det_ratio: float, what: str = "triangulate"):
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.decode.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    B, V, J = (int(v) for v in coords.shape[:3])
+    if not 2 <= V <= 4:
+        raise ValueError(f"egorear_amd.decode.{what}: 2 to 4 views are supported, got {V}")
+    if B < 1 or J < 1:
+        raise ValueError(f"egorear_amd.decode.{what}: empty coords {tuple(coords.shape)}")
+    if tuple(conf.shape) != (B, V, J):
+        raise ValueError(f"egorear_amd.decode.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
+    if tuple(cams.shape) != (V, hip.RAY_REC):
+        raise ValueError(f"egorear_amd.decode.{what}: {V} views need {V} camera records of {hip.RAY_REC} floats, got {tuple(cams.shape)}")
+    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
+        raise ValueError(f"egorear_amd.decode.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
+    for t, name in ((coords, "coords"), (conf, "conf"), (cams, "camera records"), (ctm, "coord_trans_mat")):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"egorear_amd.decode.{what}: float32 {name} expected, got {t.dtype}")
+    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
+        raise ValueError(f"egorear_amd.decode.{what}: heatmap_size must be positive, got scales {(sx, sy)!r}")
+    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
+        raise ValueError(f"egorear_amd.decode.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
+    return B, V, J
+
+
+@torch.library.custom_op("egorear_amd::triangulate", mutates_args=(), device_types="cuda")
+def triangulate_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
+                   threshold: float, min_det_ratio: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pts (B, J, 3) cm, cost (B, J) cm^2, resid (B, V, J) cm, ok (B, J) uint8) of coords (B, V, J, 2) * (sx, sy) = normalised image
+    points, conf (B, V, J), cams (V, 30) = camera.packed_rays(), ctm (B, V, 4, 4) or None (the syn rig)."""
+    _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio)
+    return hip.triangulate(coords.contiguous(), conf.contiguous(), cams.contiguous(), None if ctm is None else ctm.contiguous(), sx, sy,
+                           threshold, min_det_ratio)
+
+
+@triangulate_op.register_fake
+def _triangulate_fake(coords, conf, cams, ctm, sx, sy, threshold, min_det_ratio):
+    B, V, J = _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio)
+    return (coords.new_empty((B, J, 3)), coords.new_empty((B, J)), coords.new_empty((B, V, J)), coords.new_empty((B, J), dtype=torch.uint8))
+
+
+@torch.library.custom_op("egorear_amd::triangulate_bwd", mutates_args=(), device_types="cuda")
+def triangulate_bwd_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor],
+                       g_pts: Optional[torch.Tensor], g_cost: Optional[torch.Tensor], sx: float, sy: float, threshold: float,
+                       min_det_ratio: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(g_coords (B, V, J, 2), g_conf (B, V, J)) from g_pts (B, J, 3) and g_cost (B, J), each None for zeros."""
+    _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd")
+    gp = None if g_pts is None else g_pts.to(torch.float32).contiguous()
+    gc = None if g_cost is None else g_cost.to(torch.float32).contiguous()
+    return hip.triangulate_bwd(coords.contiguous(), conf.contiguous(), cams.contiguous(), None if ctm is None else ctm.contiguous(), gp, gc,
+                               sx, sy, threshold, min_det_ratio)
+
+
+@triangulate_bwd_op.register_fake
+def _triangulate_bwd_fake(coords, conf, cams, ctm, g_pts, g_cost, sx, sy, threshold, min_det_ratio):
+    B, V, J = _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd")
+    if (g_pts is not None and tuple(g_pts.shape) != (B, J, 3)) or (g_cost is not None and tuple(g_cost.shape) != (B, J)):
+        raise ValueError(f"egorear_amd.decode.triangulate_bwd: g_pts must be {(B, J, 3)} and g_cost {(B, J)}")
+    return coords.new_empty((B, V, J, 2)), coords.new_empty((B, V, J))
+
+
+def _tri_setup_context(ctx, inputs, output):
+    coords, conf, cams, ctm, sx, sy, threshold, min_det_ratio = inputs
+    ctx.has_ctm = ctm is not None
+    ctx.save_for_backward(*((coords, conf, cams) + ((ctm,) if ctx.has_ctm else ())))
+    ctx.args = (sx, sy, threshold, min_det_ratio)
+    ctx.mark_non_differentiable(output[2])       # resid (ok is not a floating-point tensor)
+
+
+def _tri_autograd(ctx, g_pts, g_cost, g_resid, g_ok):
+    coords, conf, cams = ctx.saved_tensors[:3]
+    ctm = ctx.saved_tensors[3] if ctx.has_ctm else None
+    g_coords, g_conf = triangulate_bwd_op(coords, conf, cams, ctm, g_pts, g_cost, *ctx.args)
+    return g_coords, g_conf, None, None, None, None, None, None
+
+
+triangulate_op.register_autograd(_tri_autograd, setup_context=_tri_setup_context)
+
+
+class Joints3D(NamedTuple):
+    pose: torch.Tensor       # (B, J, 3) cm, device frame; 0 where not valid
+    cost: torch.Tensor       # (B, J) weighted mean squared ray distance, cm^2
+    residual: torch.Tensor   # (B, V, J) distance of the point from each view's ray, cm; 0 for excluded views
+    valid: torch.Tensor      # (B, J) bool: at least two views carried weight and the rays were not parallel
+
+
+def _ray_records(cameras: Union[str, Sequence], calib_dir: Optional[str], device: torch.device) -> torch.Tensor:
+    """(V, 30) fp32 records of the cameras on `device`, uploaded once per (cameras, device).  A warm cache is a dictionary lookup,
+    which traces; the upload itself is kept out of a traced graph."""
+    if isinstance(cameras, str):
+        key = (cameras, calib_dir or _PKG_CALIB, str(device))
+    else:
+        cameras = tuple(cameras)
+        key = tuple(id(c) for c in cameras) + (str(device),)
+    hit = _RAY_RECORDS.get(key)
+    return hit[1] if hit is not None else _upload_ray_records(cameras, key, device)
+
+
+@torch._dynamo.disable
+def _upload_ray_records(cameras, key, device) -> torch.Tensor:
+    import numpy as np
+    if isinstance(cameras, str):
+        from .camera import FishEyeCameraCalibratedModel
+        cameras = tuple(FishEyeCameraCalibratedModel(cameras, key[1], n) for n in _CAMERA_NAMES)
+    if not 2 <= len(cameras) <= 4:
+        raise ValueError(f"egorear_amd.decode.triangulate_joints: 2 to 4 cameras are supported, got {len(cameras)}")
+    rec = torch.from_numpy(np.stack([c.packed_rays() for c in cameras])).to(device)
+    _RAY_RECORDS[key] = (cameras, rec)       # (the cameras are kept: their ids are the key)
+    return rec
+
+
+def _scales(heatmap_size) -> Tuple[float, float]:
+    try:
+        H, W = (float(v) for v in heatmap_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.decode.triangulate_joints: heatmap_size must be (H, W), got {heatmap_size!r}") from None
+    if not (H > 0.0 and W > 0.0 and math.isfinite(H) and math.isfinite(W)):
+        raise ValueError(f"egorear_amd.decode.triangulate_joints: heatmap_size must be positive, got {heatmap_size!r}")
+    return 1.0 / W, 1.0 / H
+
+
+def triangulate_joints(coords: torch.Tensor, conf: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                       heatmap_size: Tuple[float, float] = (64, 64), threshold: float = 0.5, min_det_ratio: float = 1e-6,
+                       camera_calib_file_dir_path: Optional[str] = None) -> Joints3D:
+    """coords (B, V, J, 2) = (x, y) in pixels of a `heatmap_size` = (H, W) map (anchors in [0, 1]: heatmap_size (1, 1)), conf (B, V, J)
+    -> Joints3D(pose, cost, residual, valid): per joint the point closest, in the conf-weighted least-squares sense, to the V fisheye
+    rays; a view counts when its conf >= threshold and its coordinates are finite.  `cameras`: 2 to 4 FishEyeCameraCalibratedModel in
+    view order, or a camera_model string ("ego4view_syn" / "ego4view_rw": the four packaged calibrations, or those of
+    `camera_calib_file_dir_path`).  Without `coord_trans_mat` the ego4view_syn rig places the cameras (each on its own: the offsets do
+    not chain); with it (B, V, 4, 4), device frame (m) -> camera frame as in the rw models.  One launch; pose and cost are
+    differentiable with respect to coords and conf."""
+    sx, sy = _scales(heatmap_size)
+    if not (float(min_det_ratio) >= 0.0 and math.isfinite(float(min_det_ratio))):
+        raise ValueError(f"egorear_amd.decode.triangulate_joints: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
+    if coords.dim() != 4 or not 2 <= coords.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.triangulate_joints: coords must be (B, V, J, 2) with 2 to 4 views, got {tuple(coords.shape)}")
+    cams = _ray_records(cameras, camera_calib_file_dir_path, coords.device)
+    _check_tri(coords, conf, cams, coord_trans_mat, sx, sy, float(min_det_ratio), "triangulate_joints")
+    for t in (coords, conf, coord_trans_mat):
+        if t is not None:
+            _on_device(t, "triangulate_joints")
+    pts, cost, resid, ok = triangulate_op(coords, conf, cams, coord_trans_mat, sx, sy, float(threshold), float(min_det_ratio))
+    return Joints3D(pts, cost, resid, ok.view(torch.bool))
+
+
+def decode_joints_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None, beta: float = 100.0,
+                     threshold: float = 0.5, min_det_ratio: float = 1e-6, camera_calib_file_dir_path: Optional[str] = None
+                     ) -> Tuple[Joints3D, Joints2D]:
+    """heatmaps (B, V, J, H, W) -> (Joints3D, Joints2D): soft-argmax, then the triangulation of its sub-pixel joints weighted by the
+    maps' maxima - two launches with nothing between them (the pixel scale and the threshold are kernel arguments).  Gradients of
+    pose and cost reach the heat maps through both backward operators."""
+    _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="decode_joints_3d")
+    if not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.decode_joints_3d: 2 to 4 views are supported, got {tuple(heatmaps.shape)}")
+    joints2d = decode_joints_2d(heatmaps, beta=beta, threshold=threshold)
+    H, W = int(heatmaps.shape[-2]), int(heatmaps.shape[-1])
+    joints3d = triangulate_joints(joints2d.soft, joints2d.maxvals, cameras, coord_trans_mat, (H, W), threshold, min_det_ratio,
+                                  camera_calib_file_dir_path)
+    return joints3d, joints2d

@@ -184,6 +184,7 @@ EXPORTS = [
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
+    "egr_triangulate_f32", "egr_triangulate_bwd_f32",
 ]
 
 
@@ -304,6 +305,8 @@ def _load() -> C.CDLL:
     lib.egr_argmax_rows_f32.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lib.egr_soft_argmax_f32.argtypes = [vp, i32, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.egr_soft_argmax_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp, vp]
+    lib.egr_triangulate_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
+    lib.egr_triangulate_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -1263,6 +1266,73 @@ def coord_l1(coords: torch.Tensor, index: torch.Tensor, valid: torch.Tensor, wid
     _launch("egr_coord_l1_f32", lib.egr_coord_l1_f32, _p(coords), _p(index, torch.int32), _p(valid, torch.uint8), rows, int(wid), float(weight),
             _p(loss, torch.float64), _p(g), _stream(), nbytes=(13.0 + (8.0 if want_grad else 0.0)) * rows)
     return g
+
+
+RAY_REC = 30      # floats of one camera.packed_rays() record
+
+
+def _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, what: str, g_pts=None, g_cost=None):
+    """(B, V, J) of a triangulation launch; every shape / dtype / parameter error as ValueError, then the device."""
+    import math
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    B, V, J = (int(v) for v in coords.shape[:3])
+    if not 2 <= V <= 4:
+        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
+    if B < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty coords {tuple(coords.shape)}")
+    if tuple(conf.shape) != (B, V, J):
+        raise ValueError(f"egorear_amd.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
+    if tuple(cams.shape) != (V, RAY_REC):
+        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
+    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
+    for t, name in ((coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat")):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
+    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
+        raise ValueError(f"egorear_amd.{what}: the coordinate scales must be positive and finite, got {(sx, sy)!r}")
+    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
+        raise ValueError(f"egorear_amd.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
+    for t, shape, name in ((g_pts, (B, J, 3), "g_pts"), (g_cost, (B, J), "g_cost")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"egorear_amd.{what}: {name} must be a contiguous float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    for t in (coords, conf, cams, ctm, g_pts, g_cost):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"egorear_amd.{what}: no CPU path - tensors must live on the HIP device")
+    return B, V, J
+
+
+def triangulate(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None, sx: float = 1.0,
+                sy: float = 1.0, threshold: float = 0.5, min_det_ratio: float = 1e-6):
+    """coords (B,V,J,2), conf (B,V,J), cams (V,30) = camera.packed_rays(), ctm (B,V,4,4) | None (the syn rig) -> pts (B,J,3) cm,
+    cost (B,J) cm^2, resid (B,V,J) cm, ok (B,J) u8: egr_triangulate_f32, the least-squares intersection of the views' fisheye rays."""
+    B, V, J = _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate")
+    dev = coords.device
+    pts = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+    cost = torch.empty((B, J), device=dev, dtype=torch.float32)
+    resid = torch.empty((B, V, J), device=dev, dtype=torch.float32)
+    ok = torch.empty((B, J), device=dev, dtype=torch.uint8)
+    _launch("egr_triangulate_f32", lib.egr_triangulate_f32, _p(coords), _p(conf), _p(cams), _p(ctm), B, V, J, float(sx), float(sy),
+            float(threshold), float(min_det_ratio), _p(pts), _p(cost), _p(resid), _p(ok, torch.uint8), _stream(),
+            nbytes=B * J * (V * (16.0 + (64.0 if ctm is not None else 0.0)) + 17.0))
+    return pts, cost, resid, ok
+
+
+def triangulate_bwd(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], g_pts: Optional[torch.Tensor],
+                    g_cost: Optional[torch.Tensor], sx: float = 1.0, sy: float = 1.0, threshold: float = 0.5, min_det_ratio: float = 1e-6):
+    """Gradients of triangulate's pts and cost with respect to coords and conf, (B,V,J,2) and (B,V,J): egr_triangulate_bwd_f32 (the
+    forward is recomputed from the operands).  g_pts (B,J,3) and g_cost (B,J) may each be None for zeros."""
+    B, V, J = _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd", g_pts, g_cost)
+    dev = coords.device
+    g_coords = torch.empty((B, V, J, 2), device=dev, dtype=torch.float32)
+    g_conf = torch.empty((B, V, J), device=dev, dtype=torch.float32)
+    _launch("egr_triangulate_bwd_f32", lib.egr_triangulate_bwd_f32, _p(coords), _p(conf), _p(cams), _p(ctm), B, V, J, float(sx), float(sy),
+            float(threshold), float(min_det_ratio), _p(g_pts), _p(g_cost), _p(g_coords), _p(g_conf), _stream(),
+            nbytes=B * J * (V * (28.0 + (64.0 if ctm is not None else 0.0)) + 16.0))
+    return g_coords, g_conf
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -460,6 +460,32 @@ int egr_soft_argmax_bwd_f32(const float* hm, const float* stat, const float* coo
 int egr_coord_l1_f32(const float* coords, const int32_t* index, const uint8_t* valid, int32_t rows, int32_t wid, float weight,
                      double* loss, float* g_coords /* nullable */, void* stream);
 
+/* Fisheye triangulation: inverts utils/camera_models.py:53-104 (world2camera_pytorch, for one camera at a time - the syn rig is NOT
+ * chained here, SURVEY.md F7 is a property of how the lifting head calls the projection) and intersects the rays.
+ *   coords (B, V, J, 2) = (x, y) with the normalised image point (x*sx, y*sy) (heat-map pixels: sx = 1/W_hm, sy = 1/H_hm; anchors:
+ *   sx = sy = 1); conf (B, V, J): a view weighs w = conf when conf >= threshold, conf > 0 and its operands are finite, else 0.
+ *   cams: V records of 30 floats [npoly, cx, cy, W, H, W2C[12], nc2w, C2W[8], flip, off_x, off_y, off_z] (camera.packed_rays()).
+ *   Ray: rho = |(u*W - cx, v*H - cy)|, theta from atan(C2W(rho)/rho) refined by two Newton steps on W2C(theta) = rho,
+ *   d = (dx/rho cos, dy/rho cos, -sin); within 1e-4 pixels of the centre d = (0, 0, 1).
+ *   Extrinsics p_cam = R p + t: ctm == NULL (syn) R = diag(f, f, 1), f = -1 where flip, t = the offset (cm); else ctm (B, V, 4, 4) in
+ *   the rw convention of egr_fisheye_project_f32, p_cam = (M . [p*0.01, 1]) * 100.
+ *   With P = I - d d^T:  A = sum w R^T P R,  b = -sum w R^T P t,  A p = b by LDL^T.
+ * pts (B, J, 3) cm; cost (B, J) = sum w r^2 / sum w with r_v = |P_v (R_v p + t_v)| (cm^2); resid (B, V, J) = r_v, 0 for excluded
+ * views; ok (B, J) = at least two views carry weight and det A > min_det_ratio * (tr A / 3)^3 - where 0, pts / cost / resid are 0.
+ * One thread per (frame, joint), 64-thread workgroups, fp64 arithmetic on fp32 operands, no atomics: the same bits every run.
+ * EGR_EINVAL: V outside 2..4, B or J < 1, sx / sy not positive finite, threshold NaN, min_det_ratio negative or not finite. */
+int egr_triangulate_f32(const float* coords, const float* conf, const float* cams, const float* ctm /* nullable */, int32_t B, int32_t V,
+                        int32_t J, float sx, float sy, float threshold, float min_det_ratio, float* pts /* B x J x 3 */,
+                        float* cost /* B x J */, float* resid /* B x V x J */, uint8_t* ok /* B x J */, void* stream);
+/* Backward of the above (the inverse of utils/camera_models.py:53-104 differentiated): from g_pts (B, J, 3) and g_cost (B, J), either
+ * NULL for zeros, g_coords (B, V, J, 2) and g_conf (B, V, J); zero for excluded views and where ok is 0.  Through the solve
+ * dp = A^-1 (db - dA p), through the cost at fixed p (the envelope theorem), through the ray with dtheta/drho = 1 / W2C'(theta).
+ * The forward is recomputed from the operands (same code, same bits); a thread owns its pair's V gradients: no atomics. */
+int egr_triangulate_bwd_f32(const float* coords, const float* conf, const float* cams, const float* ctm /* nullable */, int32_t B,
+                            int32_t V, int32_t J, float sx, float sy, float threshold, float min_det_ratio,
+                            const float* g_pts /* nullable */, const float* g_cost /* nullable */, float* g_coords, float* g_conf,
+                            void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
