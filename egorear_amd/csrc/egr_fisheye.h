@@ -59,4 +59,30 @@ __device__ __forceinline__ void fisheye_joint(float& x, float& y, float& z, cons
     }
 }
 
+// The W2C polynomial as fisheye_one evaluates it - rho = sum_i a_i * theta^i, left to right from 0 - in the arithmetic T of the
+// caller, over coefficients of any floating type (the fp32 record itself, or a widened copy of it).
+template <typename T, typename C>
+__device__ __forceinline__ T w2c_rho(const C* coef, int npoly, T theta) {
+    T rho = (T)0, pw = (T)1;
+    for (int i = 0; i < npoly; ++i) {
+        rho = rho + (T)coef[i] * pw;
+        pw *= theta;
+    }
+    return rho;
+}
+
+// fisheye_one without the clamp and without the division by the image size (egr_volume.hip): the camera-frame point
+// (x, y, z) -> image pixels (px, py), wherever they fall.  theta = atan2(-z, norm) is defined on the optical axis too, where the
+// direction (x, y) / norm counts as (0, 0); false - and no pixel - for the camera centre and the axis behind it.
+template <typename T, typename C>
+__device__ __forceinline__ bool fisheye_pixel(const C* coef, int npoly, T cx, T cy, T x, T y, T z, T* px, T* py) {
+    const T norm = sqrt(x * x + y * y);
+    if (norm == (T)0 && z <= (T)0) return false;
+    const T rho = w2c_rho<T, C>(coef, npoly, atan2(-z, norm));
+    const T ex = norm == (T)0 ? (T)0 : x / norm, ey = norm == (T)0 ? (T)0 : y / norm;
+    *px = ex * rho + cx;
+    *py = ey * rho + cy;
+    return true;
+}
+
 }  // namespace egrf

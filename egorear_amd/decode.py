@@ -14,6 +14,12 @@ and from `maxvals`; `index`, `valid` and the probabilities are not differentiabl
 `egr_triangulate_f32` / `egr_triangulate_bwd_f32` (DESIGN.md 5n) - operators `egorear_amd::triangulate`, `egorear_amd::triangulate_bwd`,
 differentiable in the point and the cost with respect to the coordinates and the confidences - and `decode_joints_3d` chains the two
 launches: heat maps -> Joints2D -> Joints3D, with no torch arithmetic in between.
+
+`fuse_joints_volumetric` lets the views meet before the arg-max: a voxel cube around a coarse centre per joint, every voxel centre
+projected into every camera, the heat maps sampled there, the samples fused with the views' weights and one 3-D soft-argmax taken, on
+`egr_volume_fuse_f32` / `egr_volume_fuse_bwd_f32` (DESIGN.md 5o) - operators `egorear_amd::volume_fuse`, `egorear_amd::volume_fuse_bwd`,
+differentiable in the pose and the peak score with respect to the heat maps of all views jointly (the centres and the confidences are
+constants) - and `decode_joints_3d_volumetric` chains three launches: heat maps -> Joints2D -> Joints3D -> Volume3D around its pose.
 """
 from __future__ import annotations
 
@@ -318,3 +324,133 @@ def decode_joints_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coor
     joints3d = triangulate_joints(joints2d.soft, joints2d.maxvals, cameras, coord_trans_mat, (H, W), threshold, min_det_ratio,
                                   camera_calib_file_dir_path)
     return joints3d, joints2d
+
+
+# ---- volumetric fusion --------------------------------------------------------------------------------------------------------------
+
+def _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, what: str = "volume_fuse", g_pose=None, g_peak=None):
+    # (the operators make their operands contiguous before the launch, which checks that too)
+    return hip._volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "decode." + what, g_pose, g_peak, dense=False)
+
+
+def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.contiguous()
+
+
+@torch.library.custom_op("egorear_amd::volume_fuse", mutates_args=(), device_types="cuda")
+def volume_fuse_op(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor],
+                   center_ok: Optional[torch.Tensor], grid: int, cube: float, beta: float, threshold: float
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose (B, J, 3) cm, peak (B, J), index (B, J) int32, spread (B, J) cm, ok (B, J) uint8) of hm (B, V, J, H, W), conf (B, V, J),
+    centers (B, J, 3) cm, cams (V, 30) = camera.packed_rays(), ctm (B, V, 4, 4) or None (the syn rig), center_ok (B, J) uint8 or None."""
+    hm, conf, centers, cams, ctm, center_ok = _aligned(hm), _c(conf), _c(centers), _c(cams), _c(ctm), _c(center_ok)
+    _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta)
+    return hip.volume_fuse(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, threshold)
+
+
+@volume_fuse_op.register_fake
+def _volume_fuse_fake(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, threshold):
+    B, V, J, H, W = _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta)
+    return (hm.new_empty((B, J, 3)), hm.new_empty((B, J)), hm.new_empty((B, J), dtype=torch.int32), hm.new_empty((B, J)),
+            hm.new_empty((B, J), dtype=torch.uint8))
+
+
+@torch.library.custom_op("egorear_amd::volume_fuse_bwd", mutates_args=(), device_types="cuda")
+def volume_fuse_bwd_op(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor],
+                       center_ok: Optional[torch.Tensor], g_pose: Optional[torch.Tensor], g_peak: Optional[torch.Tensor], grid: int,
+                       cube: float, beta: float, threshold: float) -> torch.Tensor:
+    """g_hm (B, V, J, H, W) from g_pose (B, J, 3) and g_peak (B, J), each None for zeros."""
+    hm, conf, centers, cams, ctm, center_ok = _aligned(hm), _c(conf), _c(centers), _c(cams), _c(ctm), _c(center_ok)
+    gp = None if g_pose is None else g_pose.to(torch.float32).contiguous()
+    gk = None if g_peak is None else g_peak.to(torch.float32).contiguous()
+    _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse_bwd", gp, gk)
+    return hip.volume_fuse_bwd(hm, conf, centers, cams, ctm, center_ok, gp, gk, grid, cube, beta, threshold)
+
+
+@volume_fuse_bwd_op.register_fake
+def _volume_fuse_bwd_fake(hm, conf, centers, cams, ctm, center_ok, g_pose, g_peak, grid, cube, beta, threshold):
+    _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse_bwd", g_pose, g_peak)
+    return hm.new_empty(hm.shape)
+
+
+def _vol_setup_context(ctx, inputs, output):
+    hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, threshold = inputs
+    ctx.has_ctm, ctx.has_ok = ctm is not None, center_ok is not None
+    ctx.save_for_backward(*((hm, conf, centers, cams) + ((ctm,) if ctx.has_ctm else ()) + ((center_ok,) if ctx.has_ok else ())))
+    ctx.args = (grid, cube, beta, threshold)
+    ctx.mark_non_differentiable(output[3])       # spread (index and ok are not floating-point tensors)
+
+
+def _vol_autograd(ctx, g_pose, g_peak, g_index, g_spread, g_ok):
+    hm, conf, centers, cams = ctx.saved_tensors[:4]
+    rest = list(ctx.saved_tensors[4:])
+    ctm = rest.pop(0) if ctx.has_ctm else None
+    center_ok = rest.pop(0) if ctx.has_ok else None
+    g_hm = volume_fuse_bwd_op(hm, conf, centers, cams, ctm, center_ok, g_pose, g_peak, *ctx.args)
+    return g_hm, None, None, None, None, None, None, None, None, None      # conf and centers are constants: the cube is placed
+
+
+volume_fuse_op.register_autograd(_vol_autograd, setup_context=_vol_setup_context)
+
+
+class Volume3D(NamedTuple):
+    pose: torch.Tensor       # (B, J, 3) cm, device frame: the centre + the softmax-weighted mean voxel offset; 0 where not valid
+    peak: torch.Tensor       # (B, J) the largest fused score of the cube
+    index: torch.Tensor      # (B, J) int32: the first voxel attaining it, (iz * G + iy) * G + ix; -1 where not valid
+    spread: torch.Tensor     # (B, J) cm: rms radius of the softmax distribution about `pose` - a cheap uncertainty
+    valid: torch.Tensor      # (B, J) bool: at least two views carried weight and the centre was usable
+
+
+def _fuse(heatmaps, centers, cams, conf, coord_trans_mat, center_ok, grid, cube_cm, beta, threshold, what) -> Volume3D:
+    if heatmaps.dim() != 5:
+        raise ValueError(f"egorear_amd.decode.{what}: heat maps must be (B, V, J, H, W), got {tuple(heatmaps.shape)}")
+    B, V, J = (int(v) for v in heatmaps.shape[:3])
+    if centers.dim() == 2 and tuple(centers.shape) == (B, 3):
+        centers = centers.unsqueeze(1).expand(B, J, 3)
+    if conf is None:
+        conf = heatmaps.new_ones((B, V, J))
+    if isinstance(grid, bool) or not isinstance(grid, int):
+        raise ValueError(f"egorear_amd.decode.{what}: grid must be an integer, got {grid!r}")
+    _check_vol(heatmaps, conf, centers, cams, coord_trans_mat, center_ok, grid, float(cube_cm), float(beta), what)
+    for t in (heatmaps, conf, centers, coord_trans_mat, center_ok):
+        if t is not None:
+            _on_device(t, what)
+    pose, peak, index, spread, ok = volume_fuse_op(heatmaps, conf, centers, cams, coord_trans_mat, center_ok, grid, float(cube_cm),
+                                                   float(beta), float(threshold))
+    return Volume3D(pose, peak, index, spread, ok.view(torch.bool))
+
+
+def fuse_joints_volumetric(heatmaps: torch.Tensor, centers: torch.Tensor, cameras: Union[str, Sequence], conf: Optional[torch.Tensor] = None,
+                           coord_trans_mat: Optional[torch.Tensor] = None, grid: int = 16, cube_cm: float = 40.0, beta: float = 100.0,
+                           threshold: float = 0.5, camera_calib_file_dir_path: Optional[str] = None) -> Volume3D:
+    """heatmaps (B, V, J, H, W), centers (B, J, 3) - or (B, 3) for every joint of a frame - in cm, device frame -> Volume3D(pose, peak,
+    index, spread, valid): a `grid`^3 voxel cube of side `cube_cm` is put around each centre, every voxel centre is projected into the V
+    fisheye cameras, the heat maps are sampled there (bilinear, zero outside), the views' samples are averaged with the weights `conf`
+    (B, V, J; None: every view weighs 1; a view counts when its conf >= threshold) and the joint is the softmax(beta * score)-weighted
+    mean voxel.  `cameras` and `coord_trans_mat` as in `triangulate_joints`.  The centres come from `decode_joints_3d` or from a
+    lifting head's pose; they and `conf` are constants - pose and peak are differentiable with respect to the heat maps, of all views
+    jointly.  One launch (V * H * W <= 16384, 2 <= grid <= 32)."""
+    if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.fuse_joints_volumetric: heat maps must be (B, V, J, H, W) with 2 to 4 views, got {tuple(heatmaps.shape)}")
+    cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
+    return _fuse(heatmaps, centers, cams, conf, coord_trans_mat, None, grid, cube_cm, beta, threshold, "fuse_joints_volumetric")
+
+
+def decode_joints_3d_volumetric(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                                grid: int = 16, cube_cm: float = 40.0, beta: float = 100.0, volume_beta: float = 100.0, threshold: float = 0.5,
+                                min_det_ratio: float = 1e-6, camera_calib_file_dir_path: Optional[str] = None
+                                ) -> Tuple[Volume3D, Joints3D, Joints2D]:
+    """heatmaps (B, V, J, H, W) -> (Volume3D, Joints3D, Joints2D): `decode_joints_3d` (soft-argmax at `beta`, triangulation), then the
+    volumetric fusion (softmax at `volume_beta`) in a cube around the detached triangulated pose, weighted by the maps' maxima - three
+    launches with no torch arithmetic between them.  A joint whose triangulation is not valid is not valid here.  The gradient of the
+    fused pose and peak reaches the heat maps through the fusion alone (the cube is placed, not learned); the triangulated pose and
+    cost keep their own gradients."""
+    _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="decode_joints_3d_volumetric")
+    if not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.decode_joints_3d_volumetric: 2 to 4 views are supported, got {tuple(heatmaps.shape)}")
+    joints3d, joints2d = decode_joints_3d(heatmaps, cameras, coord_trans_mat, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
+    # (bool -> uint8 and detach are reinterpretations: nothing is launched for them)
+    volume = _fuse(heatmaps, joints3d.pose.detach(), cams, joints2d.maxvals.detach(), coord_trans_mat, joints3d.valid.view(torch.uint8),
+                   grid, cube_cm, volume_beta, threshold, "decode_joints_3d_volumetric")
+    return volume, joints3d, joints2d

@@ -184,7 +184,7 @@ EXPORTS = [
     "egr_wstream_image_bytes", "egr_pack_wstream_f32", "egr_linear_wstream_workspace_bytes", "egr_linear_wstream_f32", "egr_conv1x1_chain_f32",
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
-    "egr_triangulate_f32", "egr_triangulate_bwd_f32",
+    "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
 ]
 
 
@@ -307,6 +307,8 @@ def _load() -> C.CDLL:
     lib.egr_soft_argmax_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp, vp]
     lib.egr_triangulate_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.egr_triangulate_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
+    lib.egr_volume_fuse_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]
+    lib.egr_volume_fuse_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -1333,6 +1335,92 @@ def triangulate_bwd(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor
             float(threshold), float(min_det_ratio), _p(g_pts), _p(g_cost), _p(g_coords), _p(g_conf), _stream(),
             nbytes=B * J * (V * (28.0 + (64.0 if ctm is not None else 0.0)) + 16.0))
     return g_coords, g_conf
+
+
+VOLUME_MAX_ELEMS = 16384      # V * H * W floats of one LDS image of egr_volume.hip: four 64 x 64 maps
+VOLUME_MIN_GRID, VOLUME_MAX_GRID = 2, 32
+
+
+def _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, what: str, g_pose=None, g_peak=None, dense: bool = True):
+    """(B, V, J, H, W) of a volumetric-fusion launch; every shape / dtype / parameter error as ValueError (dense: the operands must
+    be contiguous too - a launch reads them as they lie)."""
+    import math
+    if hm.dim() != 5:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (B, V, J, H, W), got {tuple(hm.shape)}")
+    B, V, J, H, W = (int(v) for v in hm.shape)
+    if not 2 <= V <= 4:
+        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
+    if B < 1 or J < 1 or H < 1 or W < 1:
+        raise ValueError(f"egorear_amd.{what}: empty heat maps {tuple(hm.shape)}")
+    if V * H * W > VOLUME_MAX_ELEMS:
+        raise ValueError(f"egorear_amd.{what}: the V * H * W = {V * H * W} elements of a joint's maps exceed the {VOLUME_MAX_ELEMS} the "
+                         f"kernel holds in LDS")
+    if isinstance(grid, bool) or not isinstance(grid, int) or not VOLUME_MIN_GRID <= grid <= VOLUME_MAX_GRID:
+        raise ValueError(f"egorear_amd.{what}: grid must be an integer in {VOLUME_MIN_GRID}..{VOLUME_MAX_GRID}, got {grid!r}")
+    if not (cube > 0.0 and math.isfinite(cube)):
+        raise ValueError(f"egorear_amd.{what}: the cube's side must be a positive finite number of cm, got {cube!r}")
+    if not (beta > 0.0 and math.isfinite(beta)):
+        raise ValueError(f"egorear_amd.{what}: beta must be a positive finite number, got {beta!r}")
+    if tuple(conf.shape) != (B, V, J):
+        raise ValueError(f"egorear_amd.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
+    if tuple(centers.shape) != (B, J, 3):
+        raise ValueError(f"egorear_amd.{what}: centers must be {(B, J, 3)}, got {tuple(centers.shape)}")
+    if tuple(cams.shape) != (V, RAY_REC):
+        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
+    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
+    if center_ok is not None and (tuple(center_ok.shape) != (B, J) or center_ok.dtype != torch.uint8):
+        raise ValueError(f"egorear_amd.{what}: center_ok must be a uint8 {(B, J)}, got {center_ok.dtype} {tuple(center_ok.shape)}")
+    for t, name in ((hm, "heat maps"), (conf, "conf"), (centers, "centers"), (cams, "cams"), (ctm, "coord_trans_mat")):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
+    for t, shape, name in ((g_pose, (B, J, 3), "g_pose"), (g_peak, (B, J), "g_peak")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
+            raise ValueError(f"egorear_amd.{what}: {name} must be a float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    for t, name in ((hm, "heat maps"), (conf, "conf"), (centers, "centers"), (cams, "cams"), (ctm, "coord_trans_mat"),
+                    (center_ok, "center_ok"), (g_pose, "g_pose"), (g_peak, "g_peak")):
+        if dense and t is not None and not t.is_contiguous():
+            raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
+    return B, V, J, H, W
+
+
+def _volume_on_device(what: str, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"egorear_amd.{what}: no CPU path - tensors must live on the HIP device")
+
+
+def volume_fuse(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None,
+                center_ok: Optional[torch.Tensor] = None, grid: int = 16, cube: float = 40.0, beta: float = 100.0, threshold: float = 0.5):
+    """hm (B,V,J,H,W), conf (B,V,J), centers (B,J,3) cm, cams (V,30) = camera.packed_rays(), ctm (B,V,4,4) | None (the syn rig),
+    center_ok (B,J) u8 | None -> pose (B,J,3) cm, peak (B,J), index (B,J) i32, spread (B,J) cm, ok (B,J) u8: egr_volume_fuse_f32, the
+    3-D soft-argmax of the views' heat maps sampled at the projections of a grid^3 voxel cube of side `cube` around each centre."""
+    B, V, J, H, W = _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse")
+    _volume_on_device("volume_fuse", hm, conf, centers, cams, ctm, center_ok)
+    dev = hm.device
+    pose = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+    peak = torch.empty((B, J), device=dev, dtype=torch.float32)
+    index = torch.empty((B, J), device=dev, dtype=torch.int32)
+    spread = torch.empty((B, J), device=dev, dtype=torch.float32)
+    ok = torch.empty((B, J), device=dev, dtype=torch.uint8)
+    _launch("egr_volume_fuse_f32", lib.egr_volume_fuse_f32, _p(hm), _p(conf), _p(centers), _p(cams), _p(ctm), _p(center_ok, torch.uint8),
+            B, V, J, H, W, int(grid), float(cube), float(beta), float(threshold), _p(pose), _p(peak), _p(index, torch.int32), _p(spread),
+            _p(ok, torch.uint8), _stream(), nbytes=4.0 * B * V * J * H * W + B * J * (V * 4.0 + 38.0))
+    return pose, peak, index, spread, ok
+
+
+def volume_fuse_bwd(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor],
+                    center_ok: Optional[torch.Tensor], g_pose: Optional[torch.Tensor], g_peak: Optional[torch.Tensor], grid: int = 16,
+                    cube: float = 40.0, beta: float = 100.0, threshold: float = 0.5) -> torch.Tensor:
+    """Gradient of volume_fuse's pose and peak with respect to hm, (B,V,J,H,W): egr_volume_fuse_bwd_f32 (the forward is recomputed
+    from the operands; every element is written).  g_pose (B,J,3) and g_peak (B,J) may each be None for zeros."""
+    B, V, J, H, W = _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse_bwd", g_pose, g_peak)
+    _volume_on_device("volume_fuse_bwd", hm, conf, centers, cams, ctm, center_ok, g_pose, g_peak)
+    g_hm = torch.empty((B, V, J, H, W), device=hm.device, dtype=torch.float32)
+    _launch("egr_volume_fuse_bwd_f32", lib.egr_volume_fuse_bwd_f32, _p(hm), _p(conf), _p(centers), _p(cams), _p(ctm),
+            _p(center_ok, torch.uint8), B, V, J, H, W, int(grid), float(cube), float(beta), float(threshold), _p(g_pose), _p(g_peak),
+            _p(g_hm), _stream(), nbytes=8.0 * B * V * J * H * W + B * J * (V * 4.0 + 28.0))
+    return g_hm
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

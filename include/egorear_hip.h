@@ -486,6 +486,37 @@ int egr_triangulate_bwd_f32(const float* coords, const float* conf, const float*
                             const float* g_pts /* nullable */, const float* g_cost /* nullable */, float* g_coords, float* g_conf,
                             void* stream);
 
+/* Volumetric fusion of multi-view heat maps into 3-D joints: the views meet before the arg-max.
+ *   hm (B, V, J, H, W); conf (B, V, J): a view weighs w = conf when conf >= threshold, conf > 0 and conf is finite, else 0;
+ *   centers (B, J, 3) cm, device frame; cams: V records of 30 floats (camera.packed_rays(), as for egr_triangulate_f32); ctm NULL (the
+ *   syn rig, un-chained) or (B, V, 4, 4) in the rw convention - p_cam = R p + t exactly as egr_triangulate_f32 defines R and t;
+ *   center_ok (B, J) or NULL: a 0 marks a centre that is not to be used (the `ok` of the triangulation that made it).
+ *   Voxel i = (iz*G + iy)*G + ix of the cube of side `cube` cm sits at p_i = c + o_i, o_i = ((ix+.5)/G - .5, (iy+.5)/G - .5,
+ *   (iz+.5)/G - .5) * cube.  Projection q = R p + t, n = |(qx, qy)|, theta = atan2(-qz, n), rho = W2C(theta), pixel
+ *   ((qx/n) rho + cx, (qy/n) rho + cy) - direction (0, 0) where n == 0 - heat-map coordinate (x, y) = (px * W / W_img, py * H / H_img),
+ *   unclamped; a voxel with n == 0 and qz <= 0 takes no sample from that view.  Sample s: bilinear between the integer indices around
+ *   (x, y), a corner outside the map counts 0, a non-finite coordinate gives 0.  S_i = sum_v w_v s_vi / sum_v w_v.
+ * peak (B, J) = max_i S_i; index (B, J) = the first voxel attaining it; with P = softmax_i(beta * S_i): pose (B, J, 3) = c + sum_i P_i o_i
+ * and spread (B, J) = sqrt(sum_i P_i |o_i - (pose - c)|^2), cm.  ok (B, J) = at least two views carry weight, the centre is finite and
+ * center_ok allows it - where 0: pose = peak = spread = 0 and index = -1.
+ * One 512-thread workgroup per (frame, joint), the pair's maps staged in LDS once, an online softmax per thread, the records merged
+ * in a fixed order; fp64 arithmetic on fp32 operands, no atomics: the same bits every run, alone or in a batch.
+ * EGR_EINVAL: V outside 2..4, G outside 2..32, V*H*W > 16384, B / J / H / W < 1, cube or beta not positive finite, threshold NaN. */
+int egr_volume_fuse_f32(const float* hm, const float* conf, const float* centers, const float* cams, const float* ctm /* nullable */,
+                        const uint8_t* center_ok /* nullable */, int32_t B, int32_t V, int32_t J, int32_t H, int32_t W, int32_t G,
+                        float cube, float beta, float threshold, float* pose /* B x J x 3 */, float* peak /* B x J */,
+                        int32_t* index /* B x J */, float* spread /* B x J */, uint8_t* ok /* B x J */, void* stream);
+/* Backward of the above with respect to hm (conf and centers are constants: the cube is placed, not learned): from g_pose (B, J, 3) and
+ * g_peak (B, J), either NULL for zeros, g_hm (B, V, J, H, W).  gS_i = beta P_i ((o_i - (pose - c)) . g_pose) + [i == index] g_peak,
+ * and each of the four corners of each view's sample receives gS_i * w_v / sum w * (its bilinear weight); zero for excluded views and
+ * where ok is 0.  One 1024-thread workgroup per (frame, joint); the scores are recomputed from the maps in LDS (the forward's code),
+ * the gradients of the pair's maps are summed in a second LDS image (fp32 LDS adds, whose order is not fixed: the last bits may differ
+ * between runs) and every element of g_hm is written once with a plain store - no global atomics, g_hm need not be zeroed. */
+int egr_volume_fuse_bwd_f32(const float* hm, const float* conf, const float* centers, const float* cams, const float* ctm /* nullable */,
+                            const uint8_t* center_ok /* nullable */, int32_t B, int32_t V, int32_t J, int32_t H, int32_t W, int32_t G,
+                            float cube, float beta, float threshold, const float* g_pose /* nullable */,
+                            const float* g_peak /* nullable */, float* g_hm, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
