@@ -275,3 +275,177 @@ extern "C" int egr_triangulate_bwd_f32(const float* coords, const float* conf, c
                        pairs, V, J, sx, sy, threshold, min_det_ratio, g_pts, g_cost, g_coords, g_conf);
     return egr_launch_status();
 }
+
+// ------------------------------------------------------------------ consensus over candidate peaks
+// Every view brings up to K candidate image points per joint (egr_peaks_f32); a hypothesis is one candidate from each of two views,
+// h = (pair(a, b) * K + ka) * K + kb with the pairs in lexicographic order.  Its point is the two-ray least-squares intersection above
+// (weights: the two scores, the same `ok`), projected into every view with the unclamped fisheye_pixel; a view supports it with
+// its best  score * max(0, 1 - e^2 / tau^2),  e the distance (coords units) between the projection and the candidate.  The winner is
+// the largest sum of the views' support among hypotheses that at least `min_views` views support, ties to the smaller h.
+//
+// One wave per (frame, joint), lanes = hypotheses (6 K^2 <= 96: two passes at K = 4).  The first V * K lanes build the candidates'
+// rays once - the trigonometry - and park them in LDS, V more lanes the extrinsics; every lane then solves its pair and projects into
+// the V views; one fixed-order butterfly (larger score, ties to the smaller h) picks the winner, whose lane writes the outputs.  fp64
+// throughout, as above: a score's rounding decides a selection.  No atomics, a pair's bits depend on its own operands only.
+#include "egr_fisheye.h"
+
+namespace {
+
+constexpr int CON_MAX_K = 4;
+constexpr int CON_NONE = 0x7fffffff;
+
+struct con_cand {
+    double d[3];     // unit ray, camera frame
+    double w;        // the score; 0: the candidate does not exist
+    double x, y;     // coords units
+};
+
+__device__ __forceinline__ void con_add_ray(const double* R, const double* t, const con_cand& c, double& a00, double& a01, double& a02,
+                                            double& a11, double& a12, double& a22, double* rhs) {
+    // tri_solve's accumulation of one view: G = R^T R - e e^T with e = R^T d;  h = R^T t - e (d . t)
+    double e[3], rt[3];
+    const double dt = c.d[0] * t[0] + c.d[1] * t[1] + c.d[2] * t[2];
+    for (int k = 0; k < 3; ++k) {
+        e[k] = R[k] * c.d[0] + R[3 + k] * c.d[1] + R[6 + k] * c.d[2];
+        rt[k] = R[k] * t[0] + R[3 + k] * t[1] + R[6 + k] * t[2];
+    }
+#define CON_RR(k, l) (R[k] * R[l] + R[3 + k] * R[3 + l] + R[6 + k] * R[6 + l])
+    a00 += c.w * (CON_RR(0, 0) - e[0] * e[0]);
+    a01 += c.w * (CON_RR(0, 1) - e[0] * e[1]);
+    a02 += c.w * (CON_RR(0, 2) - e[0] * e[2]);
+    a11 += c.w * (CON_RR(1, 1) - e[1] * e[1]);
+    a12 += c.w * (CON_RR(1, 2) - e[1] * e[2]);
+    a22 += c.w * (CON_RR(2, 2) - e[2] * e[2]);
+#undef CON_RR
+    for (int k = 0; k < 3; ++k) rhs[k] -= c.w * (rt[k] - e[k] * dt);
+}
+
+__global__ __launch_bounds__(64) void consensus_kernel(const float* cand, const float* cscore, const int32_t* cindex, const float* cams,
+                                                       const float* ctm, int V, int J, int K, float sx, float sy, float tau, int min_views,
+                                                       float min_det_ratio, int32_t* choice, float* sel_coords, float* sel_conf,
+                                                       float* score, int32_t* inliers, int32_t* hyp) {
+    __shared__ con_cand s_c[TRI_MAX_V * CON_MAX_K];
+    __shared__ double s_R[TRI_MAX_V][9], s_t[TRI_MAX_V][3];
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int b = pair / J, j = pair - b * J;
+    if (lane < V * K) {
+        const int v = lane / K, k = lane - v * K;
+        const int64_t at = (((int64_t)b * V + v) * J + j) * K + k;
+        tri_ray ry;
+        // (threshold 0: the score must be positive and finite, the coordinates finite - tri_make_ray's own test)
+        tri_make_ray(cand, cscore, cams + v * TRI_REC, at, (double)sx, (double)sy, 0.f, ry);
+        const bool exists = cindex[at] >= 0 && ry.w != 0.0;
+        con_cand c;
+        c.w = exists ? ry.w : 0.0;
+        c.d[0] = ry.d[0];
+        c.d[1] = ry.d[1];
+        c.d[2] = ry.d[2];
+        c.x = exists ? (double)cand[at * 2 + 0] : 0.0;
+        c.y = exists ? (double)cand[at * 2 + 1] : 0.0;
+        s_c[lane] = c;
+    } else if (lane >= 32 && lane < 32 + V) {
+        const int v = lane - 32;
+        double R[9], t[3];
+        tri_extrinsics(cams + v * TRI_REC, ctm, (int64_t)b * V + v, R, t);
+        for (int i = 0; i < 9; ++i) s_R[v][i] = R[i];
+        for (int i = 0; i < 3; ++i) s_t[v][i] = t[i];
+    }
+    __syncthreads();
+
+    const int kk = K * K, nhyp = (V * (V - 1) / 2) * kk;
+    const double tau2 = (double)tau * (double)tau;
+    double my = -1.0;             // a hypothesis that qualifies scores > 0
+    int myh = CON_NONE, mypack = 0, myinl = 0;
+    for (int h = lane; h < nhyp; h += 64) {
+        const int pi = h / kk, rem = h - pi * kk, ka = rem / K, kb = rem - ka * K;
+        int va = 0, left = pi;
+        for (int n = V - 1; n > 1 && left >= n; --n) { left -= n; ++va; }
+        const int vb = va + 1 + left;
+        const con_cand ca = s_c[va * K + ka], cb = s_c[vb * K + kb];
+        if (ca.w == 0.0 || cb.w == 0.0) continue;
+        double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, rhs[3] = {0, 0, 0};
+        con_add_ray(s_R[va], s_t[va], ca, a00, a01, a02, a11, a12, a22, rhs);
+        con_add_ray(s_R[vb], s_t[vb], cb, a00, a01, a02, a11, a12, a22, rhs);
+        tri_solution s;
+        s.d1 = a00;
+        s.l21 = a01 / s.d1;
+        s.l31 = a02 / s.d1;
+        s.d2 = a11 - s.l21 * a01;
+        s.l32 = (a12 - s.l31 * a01) / s.d2;
+        s.d3 = a22 - s.l31 * a02 - s.l32 * s.l32 * s.d2;
+        const double det = s.d1 * s.d2 * s.d3, tr3 = (a00 + a11 + a22) / 3.0;
+        if (!(s.d1 > 0.0 && s.d2 > 0.0 && s.d3 > 0.0 && det > (double)min_det_ratio * tr3 * tr3 * tr3)) continue;
+        double p[3];
+        tri_ldl_solve(s, rhs, p);
+        double total = 0.0;
+        int inl = 0, pack = 0;
+        for (int v = 0; v < V; ++v) {
+            const float* cam = cams + v * TRI_REC;
+            double q[3];
+            tri_apply(s_R[v], s_t[v], p, q);
+            int nw = (int)cam[0];
+            nw = nw < 0 ? 0 : (nw > TRI_MAX_W2C ? TRI_MAX_W2C : nw);
+            double px, py;
+            if (!egrf::fisheye_pixel<double, float>(cam + TRI_W2C, nw, (double)cam[1], (double)cam[2], q[0], q[1], q[2], &px, &py)) continue;
+            const double u = px / ((double)sx * (double)cam[3]), w = py / ((double)sy * (double)cam[4]);
+            double best = 0.0;
+            int bk = -1;
+            for (int k = 0; k < K; ++k) {
+                const con_cand& c = s_c[v * K + k];
+                if (c.w == 0.0) continue;
+                const double dx = u - c.x, dy = w - c.y;
+                const double keep = 1.0 - (dx * dx + dy * dy) / tau2;
+                const double term = keep > 0.0 ? c.w * keep : 0.0;      // (NaN fails the comparison)
+                if (term > best) { best = term; bk = k; }
+            }
+            if (bk >= 0) {
+                total += best;
+                ++inl;
+                pack |= (bk + 1) << (4 * v);
+            }
+        }
+        if (inl >= min_views && total > my) {     // (the lane's own hypotheses come in increasing h: '>' keeps the first)
+            my = total;
+            myh = h;
+            mypack = pack;
+            myinl = inl;
+        }
+    }
+    double ws = my;
+    int wh = myh;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double os = __shfl_xor(ws, o, 64);
+        const int oh = __shfl_xor(wh, o, 64);
+        if (os > ws || (os == ws && oh < wh)) { ws = os; wh = oh; }
+    }
+    const bool none = wh == CON_NONE;
+    if (none ? lane == 0 : myh == wh) {
+        for (int v = 0; v < V; ++v) {
+            const int k = none ? -1 : ((mypack >> (4 * v)) & 7) - 1;
+            const int64_t o = ((int64_t)b * V + v) * J + j;
+            choice[o] = k;
+            sel_coords[o * 2 + 0] = k >= 0 ? cand[(o * K + k) * 2 + 0] : 0.f;
+            sel_coords[o * 2 + 1] = k >= 0 ? cand[(o * K + k) * 2 + 1] : 0.f;
+            sel_conf[o] = k >= 0 ? cscore[o * K + k] : 0.f;
+        }
+        score[pair] = none ? 0.f : (float)ws;
+        inliers[pair] = none ? 0 : myinl;
+        hyp[pair] = none ? -1 : wh;
+    }
+}
+
+}  // namespace
+
+extern "C" int egr_consensus_f32(const float* cand, const float* cscore, const int32_t* cindex, const float* cams, const float* ctm, int32_t B,
+                                 int32_t V, int32_t J, int32_t K, float sx, float sy, float max_reproj, int32_t min_views,
+                                 float min_det_ratio, int32_t* choice, float* sel_coords, float* sel_conf, float* score, int32_t* inliers,
+                                 int32_t* hyp, void* stream) {
+    if (!cand || !cscore || !cindex || !cams || !choice || !sel_coords || !sel_conf || !score || !inliers || !hyp) return EGR_ENULL;
+    if (!tri_shape_ok(B, V, J, sx, sy, 0.f, min_det_ratio) || K < 1 || K > CON_MAX_K || (int64_t)B * J * V * K >= (1 << 30) ||
+        !(max_reproj > 0.f && max_reproj <= 3.0e38f) || min_views < 2 || min_views > V)
+        return EGR_EINVAL;
+    hipLaunchKernelGGL(consensus_kernel, dim3((unsigned)(B * J)), dim3(64), 0, (hipStream_t)stream, cand, cscore, cindex, cams, ctm, V, J, K,
+                       sx, sy, max_reproj, min_views, min_det_ratio, choice, sel_coords, sel_conf, score, inliers, hyp);
+    return egr_launch_status();
+}

@@ -20,6 +20,12 @@ projected into every camera, the heat maps sampled there, the samples fused with
 `egr_volume_fuse_f32` / `egr_volume_fuse_bwd_f32` (DESIGN.md 5o) - operators `egorear_amd::volume_fuse`, `egorear_amd::volume_fuse_bwd`,
 differentiable in the pose and the peak score with respect to the heat maps of all views jointly (the centres and the confidences are
 constants) - and `decode_joints_3d_volumetric` chains three launches: heat maps -> Joints2D -> Joints3D -> Volume3D around its pose.
+
+`find_peaks_2d` keeps the K best local maxima of every map instead of its global one, `select_consistent` picks per joint the
+candidates the views agree on - every two-view pair of candidates is triangulated and scored by how well the views' candidates
+support its reprojections - on `egr_peaks_f32` / `egr_consensus_f32` (DESIGN.md 5p), operators `egorear_amd::find_peaks`,
+`egorear_amd::consensus`, neither differentiable - and `decode_joints_3d_robust` chains three launches: heat maps -> Peaks2D ->
+Consensus -> Joints3D of the accepted views, so that one view firing on a second mode is out-voted instead of bending the pose.
 """
 from __future__ import annotations
 
@@ -454,3 +460,131 @@ def decode_joints_3d_volumetric(heatmaps: torch.Tensor, cameras: Union[str, Sequ
     volume = _fuse(heatmaps, joints3d.pose.detach(), cams, joints2d.maxvals.detach(), coord_trans_mat, joints3d.valid.view(torch.uint8),
                    grid, cube_cm, volume_beta, threshold, "decode_joints_3d_volumetric")
     return volume, joints3d, joints2d
+
+
+# ---- multi-peak decoding and consensus triangulation --------------------------------------------------------------------------------
+
+def _refuse_cpu(what: str, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda and t.device.type != "meta":
+            raise ValueError(f"egorear_amd.decode.{what}: no CPU path - tensors must live on the HIP device")
+
+
+@torch.library.custom_op("egorear_amd::find_peaks", mutates_args=(), device_types="cuda")
+def find_peaks_op(hm: torch.Tensor, k: int, nms_radius: int, refine_radius: int, beta: float, threshold: float
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(coords (..., k, 2) heat-map pixels, score (..., k), index (..., k) int32, count (...) int32) of hm (..., H, W), H * W <= 4096:
+    egr_peaks_f32.  No output is differentiable: there is no gradient through the selection or the window refinement."""
+    lead, _, _, _ = hip._peaks_operands(hm, k, nms_radius, refine_radius, beta, threshold, "decode.find_peaks", dense=False)
+    coords, score, index, count = hip.find_peaks(_aligned(hm), k, nms_radius, refine_radius, beta, threshold)
+    return coords.view(lead + (k, 2)), score.view(lead + (k,)), index.view(lead + (k,)), count.view(lead)
+
+
+@find_peaks_op.register_fake
+def _find_peaks_fake(hm, k, nms_radius, refine_radius, beta, threshold):
+    lead, _, _, _ = hip._peaks_operands(hm, k, nms_radius, refine_radius, beta, threshold, "decode.find_peaks", dense=False)
+    return (hm.new_empty(lead + (k, 2)), hm.new_empty(lead + (k,)), hm.new_empty(lead + (k,), dtype=torch.int32),
+            hm.new_empty(lead, dtype=torch.int32))
+
+
+@torch.library.custom_op("egorear_amd::consensus", mutates_args=(), device_types="cuda")
+def consensus_op(cand: torch.Tensor, cscore: torch.Tensor, cindex: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float,
+                 sy: float, max_reproj: float, min_views: int, min_det_ratio: float
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(choice (B, V, J) int32, sel_coords (B, V, J, 2), sel_conf (B, V, J), score (B, J), inliers (B, J) int32, hyp (B, J) int32) of the
+    candidates cand (B, V, J, K, 2), cscore (B, V, J, K), cindex (B, V, J, K) int32, cams (V, 30), ctm (B, V, 4, 4) or None:
+    egr_consensus_f32.  No output is differentiable: the selection is a discrete choice, its coordinates are copies."""
+    hip._consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, "decode.consensus", dense=False)
+    return hip.consensus(_c(cand), _c(cscore), _c(cindex), _c(cams), _c(ctm), sx, sy, max_reproj, min_views, min_det_ratio)
+
+
+@consensus_op.register_fake
+def _consensus_fake(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio):
+    B, V, J, K = hip._consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, "decode.consensus",
+                                         dense=False)
+    return (cand.new_empty((B, V, J), dtype=torch.int32), cand.new_empty((B, V, J, 2)), cand.new_empty((B, V, J)), cand.new_empty((B, J)),
+            cand.new_empty((B, J), dtype=torch.int32), cand.new_empty((B, J), dtype=torch.int32))
+
+
+def _nograd_setup_context(ctx, inputs, output):
+    ctx.n_inputs = len(inputs)
+    ctx.mark_non_differentiable(*(t for t in output if t.is_floating_point()))
+
+
+def _nograd_autograd(ctx, *grads):
+    return (None,) * ctx.n_inputs
+
+
+find_peaks_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+consensus_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+
+
+class Peaks2D(NamedTuple):
+    coords: torch.Tensor     # (B, V, J, K, 2) refined (x, y), heat-map pixels, best peak first; 0 in unfilled slots
+    score: torch.Tensor      # (B, V, J, K) the peaks' own values; 0 in unfilled slots
+    index: torch.Tensor      # (B, V, J, K) int32 flat index of the peak pixel; -1 in unfilled slots
+    count: torch.Tensor      # (B, V, J) int32 peaks kept, 0..K
+
+
+class Consensus(NamedTuple):
+    coords: torch.Tensor      # (B, V, J, 2) the chosen candidate of every view, copied; 0 where the view has no choice
+    conf: torch.Tensor        # (B, V, J) its score; 0 where the view has no choice
+    choice: torch.Tensor      # (B, V, J) int32 its slot k, or -1
+    score: torch.Tensor       # (B, J) the winning hypothesis's support, summed over the views
+    inliers: torch.Tensor     # (B, J) int32 views with a choice
+    hypothesis: torch.Tensor  # (B, J) int32 (pair(a, b) * K + ka) * K + kb of the winner, or -1 when nothing qualifies
+
+
+def find_peaks_2d(heatmaps: torch.Tensor, k: int = 3, nms_radius: int = 1, refine_radius: int = 2, beta: float = 100.0,
+                  threshold: float = 0.5) -> Peaks2D:
+    """heatmaps (B, V, J, H, W), H * W <= 4096 -> Peaks2D(coords, score, index, count): per map the `k` (1..4) best local maxima above
+    `threshold` - a pixel that beats its (2 nms_radius + 1)^2 neighbourhood, a plateau counting once at its first pixel - ordered by value,
+    each refined to sub-pixel by the softmax(beta h)-weighted mean over its (2 refine_radius + 1)^2 window.  One launch, one read of the
+    maps.  Nothing here is differentiable."""
+    if heatmaps.dim() != 5:
+        raise ValueError(f"egorear_amd.decode.find_peaks_2d: heat maps must be (B, V, J, H, W), got {tuple(heatmaps.shape)}")
+    hip._peaks_operands(heatmaps, k, nms_radius, refine_radius, float(beta), float(threshold), "decode.find_peaks_2d", dense=False)
+    _refuse_cpu("find_peaks_2d", heatmaps)
+    return Peaks2D(*find_peaks_op(heatmaps, k, nms_radius, refine_radius, float(beta), float(threshold)))
+
+
+def select_consistent(peaks: Peaks2D, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                      heatmap_size: Tuple[float, float] = (64, 64), max_reproj: float = 2.0, min_views: int = 2, min_det_ratio: float = 1e-6,
+                      camera_calib_file_dir_path: Optional[str] = None) -> Consensus:
+    """peaks = find_peaks_2d's result over maps of `heatmap_size` = (H, W) -> Consensus(coords, conf, choice, score, inliers,
+    hypothesis): per (frame, joint) every pair of candidates from two views is triangulated, the point is projected back into all views
+    and each view supports it with its best  score * max(0, 1 - e^2 / max_reproj^2)  (e: heat-map pixels); the best-supported point
+    that at least `min_views` views support picks one candidate - or none - per view.  `coords` / `conf` are the operands
+    `triangulate_joints` takes.  `cameras` and `coord_trans_mat` as there.  One launch.  Nothing here is differentiable."""
+    sx, sy = _scales(heatmap_size)
+    cand, cscore, cindex = peaks[0], peaks[1], peaks[2]
+    if cand.dim() != 5 or not 2 <= cand.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.select_consistent: candidates must be (B, V, J, K, 2) with 2 to 4 views, got {tuple(cand.shape)}")
+    cams = _ray_records(cameras, camera_calib_file_dir_path, cand.device)
+    hip._consensus_operands(cand, cscore, cindex, cams, coord_trans_mat, sx, sy, float(max_reproj), min_views, float(min_det_ratio),
+                            "decode.select_consistent", dense=False)
+    _refuse_cpu("select_consistent", cand, cscore, cindex, coord_trans_mat)
+    choice, sel_coords, sel_conf, score, inliers, hyp = consensus_op(cand, cscore, cindex, cams, coord_trans_mat, sx, sy, float(max_reproj),
+                                                                     min_views, float(min_det_ratio))
+    return Consensus(sel_coords, sel_conf, choice, score, inliers, hyp)
+
+
+def decode_joints_3d_robust(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None, k: int = 3,
+                            nms_radius: int = 1, refine_radius: int = 2, beta: float = 100.0, threshold: float = 0.5,
+                            max_reproj: float = 2.0, min_views: int = 2, min_det_ratio: float = 1e-6,
+                            camera_calib_file_dir_path: Optional[str] = None) -> Tuple[Joints3D, Consensus, Peaks2D]:
+    """heatmaps (B, V, J, H, W) -> (Joints3D, Consensus, Peaks2D): the `k` best peaks of every map, the candidates the views agree on,
+    then `triangulate_joints` of those - three launches with no torch operation between them (the consensus writes the
+    triangulation's operands).  A view whose map fired on a second mode is out-voted by the others instead of bending the pose;
+    `Joints3D.residual` reports the accepted views only, and a joint without a consensus is not valid.  With two views there is no
+    third to out-vote a distractor: the consensus then only rejects pairs that do not meet.  Nothing here is differentiable."""
+    if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.decode.decode_joints_3d_robust: heat maps must be (B, V, J, H, W) with 2 to 4 views, got "
+                         f"{tuple(heatmaps.shape)}")
+    peaks = find_peaks_2d(heatmaps, k, nms_radius, refine_radius, beta, threshold)
+    H, W = int(heatmaps.shape[-2]), int(heatmaps.shape[-1])
+    agreed = select_consistent(peaks, cameras, coord_trans_mat, (H, W), max_reproj, min_views, min_det_ratio, camera_calib_file_dir_path)
+    # (a rejected view carries conf 0 and is excluded whatever the threshold; an accepted one scored above `threshold` already)
+    joints3d = triangulate_joints(agreed.coords, agreed.conf, cameras, coord_trans_mat, (H, W), threshold, min_det_ratio,
+                                  camera_calib_file_dir_path)
+    return joints3d, agreed, peaks

@@ -185,6 +185,7 @@ EXPORTS = [
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
     "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
+    "egr_peaks_f32", "egr_consensus_f32",
 ]
 
 
@@ -309,6 +310,8 @@ def _load() -> C.CDLL:
     lib.egr_triangulate_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.egr_volume_fuse_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]
     lib.egr_volume_fuse_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]
+    lib.egr_peaks_f32.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
+    lib.egr_consensus_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -1421,6 +1424,113 @@ def volume_fuse_bwd(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor,
             _p(center_ok, torch.uint8), B, V, J, H, W, int(grid), float(cube), float(beta), float(threshold), _p(g_pose), _p(g_peak),
             _p(g_hm), _stream(), nbytes=8.0 * B * V * J * H * W + B * J * (V * 4.0 + 28.0))
     return g_hm
+
+
+PEAKS_MAX_ELEMS = 4096        # H * W floats of one LDS image of egr_peaks.hip
+PEAKS_MAX_K, PEAKS_MAX_NMS, PEAKS_MAX_REFINE = 4, 3, 3
+
+
+def _int_in(v, lo: int, hi: int) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+
+
+def _peaks_operands(hm, k, nms_radius, refine_radius, beta, min_score, what: str, dense: bool = True):
+    """(lead shape, rows, H, W) of a peaks launch over (..., H, W) maps; every shape / dtype / parameter error as ValueError."""
+    import math
+    if hm.dim() < 2:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (..., H, W), got {tuple(hm.shape)}")
+    if hm.dtype != torch.float32:
+        raise ValueError(f"egorear_amd.{what}: float32 heat maps expected, got {hm.dtype}")
+    H, W = int(hm.shape[-2]), int(hm.shape[-1])
+    if hm.numel() == 0 or not 1 <= H * W <= PEAKS_MAX_ELEMS:
+        raise ValueError(f"egorear_amd.{what}: maps must hold between 1 and {PEAKS_MAX_ELEMS} elements, got {tuple(hm.shape)}")
+    if not _int_in(k, 1, PEAKS_MAX_K):
+        raise ValueError(f"egorear_amd.{what}: k must be an integer in 1..{PEAKS_MAX_K}, got {k!r}")
+    if not _int_in(nms_radius, 1, PEAKS_MAX_NMS):
+        raise ValueError(f"egorear_amd.{what}: nms_radius must be an integer in 1..{PEAKS_MAX_NMS}, got {nms_radius!r}")
+    if not _int_in(refine_radius, 0, PEAKS_MAX_REFINE):
+        raise ValueError(f"egorear_amd.{what}: refine_radius must be an integer in 0..{PEAKS_MAX_REFINE}, got {refine_radius!r}")
+    if not (beta > 0.0 and math.isfinite(beta)):
+        raise ValueError(f"egorear_amd.{what}: beta must be a positive finite number, got {beta!r}")
+    if not math.isfinite(min_score):
+        raise ValueError(f"egorear_amd.{what}: the score threshold must be finite, got {min_score!r}")
+    if dense and not hm.is_contiguous():
+        raise ValueError(f"egorear_amd.{what}: heat maps must be contiguous")
+    return tuple(hm.shape[:-2]), hm.numel() // (H * W), H, W
+
+
+def find_peaks(hm: torch.Tensor, k: int = 3, nms_radius: int = 1, refine_radius: int = 2, beta: float = 100.0, min_score: float = 0.5):
+    """hm (..., H, W) contiguous, H * W <= 4096 -> coords (rows,k,2) f32 (x, y) heat-map pixels, score (rows,k), index (rows,k) i32,
+    count (rows,) i32: egr_peaks_f32, the k best local maxima of every map (value, then smaller flat index), each refined over its
+    (2 refine_radius + 1)^2 window.  Slots past count: coords 0, score 0, index -1."""
+    _, rows, H, W = _peaks_operands(hm, k, nms_radius, refine_radius, beta, min_score, "find_peaks")
+    _volume_on_device("find_peaks", hm)
+    dev = hm.device
+    coords = torch.empty((rows, k, 2), device=dev, dtype=torch.float32)
+    score = torch.empty((rows, k), device=dev, dtype=torch.float32)
+    index = torch.empty((rows, k), device=dev, dtype=torch.int32)
+    count = torch.empty((rows,), device=dev, dtype=torch.int32)
+    _launch("egr_peaks_f32", lib.egr_peaks_f32, _p(hm), rows, H, W, int(k), int(nms_radius), int(refine_radius), float(beta), float(min_score),
+            _p(coords), _p(score), _p(index, torch.int32), _p(count, torch.int32), _stream(), nbytes=4.0 * hm.numel() + rows * (16.0 * k + 4.0))
+    return coords, score, index, count
+
+
+def _consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, what: str, dense: bool = True):
+    """(B, V, J, K) of a consensus launch; every shape / dtype / parameter error as ValueError."""
+    import math
+    if cand.dim() != 5 or cand.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.{what}: candidates must be (B, V, J, K, 2), got {tuple(cand.shape)}")
+    B, V, J, K = (int(v) for v in cand.shape[:4])
+    if not 2 <= V <= 4:
+        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
+    if not 1 <= K <= PEAKS_MAX_K:
+        raise ValueError(f"egorear_amd.{what}: 1 to {PEAKS_MAX_K} candidates per view are supported, got {K}")
+    if B < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty candidates {tuple(cand.shape)}")
+    if tuple(cscore.shape) != (B, V, J, K) or tuple(cindex.shape) != (B, V, J, K):
+        raise ValueError(f"egorear_amd.{what}: scores and indices must be {(B, V, J, K)}, got {tuple(cscore.shape)} and {tuple(cindex.shape)}")
+    if tuple(cams.shape) != (V, RAY_REC):
+        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
+    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
+    for t, name in ((cand, "candidates"), (cscore, "scores"), (cams, "cams"), (ctm, "coord_trans_mat")):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
+    if cindex.dtype != torch.int32:
+        raise ValueError(f"egorear_amd.{what}: int32 indices expected, got {cindex.dtype}")
+    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
+        raise ValueError(f"egorear_amd.{what}: the coordinate scales must be positive and finite, got {(sx, sy)!r}")
+    if not (max_reproj > 0.0 and math.isfinite(max_reproj)):
+        raise ValueError(f"egorear_amd.{what}: max_reproj must be a positive finite number, got {max_reproj!r}")
+    if not _int_in(min_views, 2, V):
+        raise ValueError(f"egorear_amd.{what}: min_views must be an integer in 2..{V}, got {min_views!r}")
+    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
+        raise ValueError(f"egorear_amd.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
+    for t, name in ((cand, "candidates"), (cscore, "scores"), (cindex, "indices"), (cams, "cams"), (ctm, "coord_trans_mat")):
+        if dense and t is not None and not t.is_contiguous():
+            raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
+    return B, V, J, K
+
+
+def consensus(cand: torch.Tensor, cscore: torch.Tensor, cindex: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None,
+              sx: float = 1.0, sy: float = 1.0, max_reproj: float = 2.0, min_views: int = 2, min_det_ratio: float = 1e-6):
+    """cand (B,V,J,K,2), cscore (B,V,J,K), cindex (B,V,J,K) i32 = find_peaks' outputs, cams (V,30), ctm (B,V,4,4) | None -> choice (B,V,J)
+    i32, sel_coords (B,V,J,2), sel_conf (B,V,J), score (B,J), inliers (B,J) i32, hyp (B,J) i32: egr_consensus_f32, per joint the
+    candidates the views agree on - the two-view hypothesis whose reprojections the views' candidates support best."""
+    B, V, J, K = _consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, "consensus")
+    _volume_on_device("consensus", cand, cscore, cindex, cams, ctm)
+    dev = cand.device
+    choice = torch.empty((B, V, J), device=dev, dtype=torch.int32)
+    sel_coords = torch.empty((B, V, J, 2), device=dev, dtype=torch.float32)
+    sel_conf = torch.empty((B, V, J), device=dev, dtype=torch.float32)
+    score = torch.empty((B, J), device=dev, dtype=torch.float32)
+    inliers = torch.empty((B, J), device=dev, dtype=torch.int32)
+    hyp = torch.empty((B, J), device=dev, dtype=torch.int32)
+    _launch("egr_consensus_f32", lib.egr_consensus_f32, _p(cand), _p(cscore), _p(cindex, torch.int32), _p(cams), _p(ctm), B, V, J, K, float(sx),
+            float(sy), float(max_reproj), int(min_views), float(min_det_ratio), _p(choice, torch.int32), _p(sel_coords), _p(sel_conf),
+            _p(score), _p(inliers, torch.int32), _p(hyp, torch.int32), _stream(),
+            nbytes=B * J * (V * (16.0 * K + 16.0 + (64.0 if ctm is not None else 0.0)) + 12.0))
+    return choice, sel_coords, sel_conf, score, inliers, hyp
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -517,6 +517,45 @@ int egr_volume_fuse_bwd_f32(const float* hm, const float* conf, const float* cen
                             float cube, float beta, float threshold, const float* g_pose /* nullable */,
                             const float* g_peak /* nullable */, float* g_hm, void* stream);
 
+/* Multi-peak decoding of heat maps: the K best local maxima of every map, refined to sub-pixel.
+ *   hm: `rows` dense maps (hgt, wid) fp32, 1 <= hgt*wid <= 4096.  A NaN compares as -inf; +-inf compare as they are; pixels outside the
+ *   map count as -inf.  Pixel i (flat index) is a peak when h_i is finite, h_i > min_score, h_i > h_n for every neighbour n < i of its
+ *   (2*nms_radius+1)^2 window and h_i >= h_n for every neighbour n > i: a plateau keeps its first pixel, a constant map the peak 0.
+ *   The K best peaks by value, ties to the smaller flat index (the rule of egr_soft_argmax_f32), are kept in that order.  A kept peak
+ *   (cm, rm) of value m is refined over its (2*refine_radius+1)^2 window clipped to the map: e_p = exp(beta (h_p - m)) for finite h_p,
+ *   else 0;  x = cm + sum e_p (col_p - cm) / sum e_p, y likewise - heat-map pixels, the convention of egr_soft_argmax_f32.
+ * coords (rows, K, 2); score (rows, K) = the peak's value, copied; index (rows, K) = its flat index; count (rows) = peaks kept.  A
+ * slot past count holds coords 0, score 0, index -1.
+ * One wave - one 64-thread workgroup - per map; the map is read once and staged in LDS; fixed-order reductions, fp64 refinement, no
+ * atomics: the same bits every run, alone or in a batch.
+ * EGR_EINVAL: hgt*wid outside 1..4096, K outside 1..4, nms_radius outside 1..3, refine_radius outside 0..3, beta not positive finite,
+ * min_score not finite. */
+int egr_peaks_f32(const float* hm, int32_t rows, int32_t hgt, int32_t wid, int32_t K, int32_t nms_radius, int32_t refine_radius, float beta,
+                  float min_score, float* coords /* rows x K x 2 */, float* score /* rows x K */, int32_t* index /* rows x K */,
+                  int32_t* count /* rows */, void* stream);
+/* Consensus over the views' candidate peaks: per (frame, joint) the candidates the views agree on.
+ *   cand (B, V, J, K, 2), cscore (B, V, J, K), cindex (B, V, J, K): the outputs of egr_peaks_f32; a candidate exists when its index is
+ *   >= 0, its score finite and > 0 and its coordinates finite.  cams, ctm, sx, sy, min_det_ratio as for egr_triangulate_f32.
+ *   Hypothesis h = (pair(a, b)*K + ka)*K + kb over the view pairs a < b in lexicographic order, both candidates existing: its point p
+ *   is egr_triangulate_f32's intersection of the two rays weighted by the two scores (the same ok).  p is projected into every view
+ *   (R p + t, the unclamped projection of egr_volume_fuse_f32) and taken to coords units by 1 / (sx W_img), 1 / (sy H_img).  View v
+ *   supports h with its largest  cscore_vk * max(0, 1 - e^2 / max_reproj^2),  e the distance between the projection and candidate k,
+ *   ties to the smaller k; its choice is that k, or -1 when the support is 0 or the projection does not exist.  score_h = the sum of
+ *   the views' support, inliers_h = the views with a choice.  The winner: the largest score among the hypotheses with inliers >=
+ *   min_views, ties to the smaller h.
+ * choice (B, V, J); sel_coords (B, V, J, 2) and sel_conf (B, V, J) = the chosen candidate's coords and score, copied, 0 where the choice
+ * is -1: the operands of egr_triangulate_f32.  score (B, J), inliers (B, J), hyp (B, J) = the winner's; hyp -1, score 0, inliers 0 and
+ * every choice -1 where no hypothesis qualifies.
+ * One wave per (frame, joint), lanes = hypotheses; fp64 arithmetic on fp32 operands, a fixed-order arg-max, no atomics: the same bits
+ * every run, alone or in a batch.
+ * EGR_EINVAL: V outside 2..4, K outside 1..4, B or J < 1, sx / sy / max_reproj not positive finite, min_views outside 2..V,
+ * min_det_ratio negative or not finite. */
+int egr_consensus_f32(const float* cand, const float* cscore, const int32_t* cindex, const float* cams, const float* ctm /* nullable */,
+                      int32_t B, int32_t V, int32_t J, int32_t K, float sx, float sy, float max_reproj, int32_t min_views,
+                      float min_det_ratio, int32_t* choice /* B x V x J */, float* sel_coords /* B x V x J x 2 */,
+                      float* sel_conf /* B x V x J */, float* score /* B x J */, int32_t* inliers /* B x J */, int32_t* hyp /* B x J */,
+                      void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
