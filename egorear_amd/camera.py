@@ -16,7 +16,7 @@ import numpy as np
 
 MAX_POLY = 12
 MAX_C2W = 8
-RAY_REC = 5 + MAX_POLY + 1 + MAX_C2W + 1 + 3
+RAY_REC = 5 + MAX_POLY + 1 + MAX_C2W + 1 + 3      # packed_rays(); the device reads it by the layout of csrc/egr_rays.h
 
 # utils/camera_models.py:29-40: constant rigid offsets (cm) used in ego4view_syn mode
 _SYN_OFFSETS = {

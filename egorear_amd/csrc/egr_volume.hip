@@ -1,6 +1,6 @@
 // Volumetric fusion of multi-view heat maps into 3-D joints: forward and backward.
 // A cube of G^3 voxels around a coarse centre; every voxel centre is projected into every camera (the projection of egr_fisheye.h,
-// unclamped; the extrinsics of egr_triangulate.hip), the heat maps are sampled there bilinearly with zero padding, the samples of the
+// unclamped; the camera record and the extrinsics of egr_rays.h), the heat maps are sampled there bilinearly with zero padding, the samples of the
 // views are fused with the views' weights, and one 3-D soft-argmax over the cube gives the joint:
 //   S_i = sum_v w_v s_{v,i} / sum_v w_v,   P = softmax(beta S),   pose = c + sum_i P_i o_i,   spread^2 = sum_i P_i |o_i - (pose - c)|^2.
 //
@@ -18,21 +18,17 @@
 //   gS_i * w_v / sum w * (bilinear weight),   gS_i = beta P_i ((o_i - (pose - c)) . g_pose) + [i == index] g_peak
 // into a second LDS image with fp32 LDS atomic adds (the order of those adds is not fixed: the last bits of g_hm may differ between
 // runs), then writes every element of g_hm once with plain stores: no global atomics, no zeroed output needed.
-#include "egr_common.h"
-#include "egr_fisheye.h"
-#include <math.h>
+#include "egr_rays.h"
 
 namespace {
 
-// camera record of camera.packed_rays(), as in egr_triangulate.hip
-constexpr int VOL_REC = 30, VOL_W2C = 5, VOL_MAX_W2C = 12, VOL_FLIP = 26, VOL_OFF = 27;
-constexpr int VOL_MAX_V = 4, VOL_MIN_G = 2, VOL_MAX_G = 32;
+constexpr int VOL_MAX_V = rays::MAX_V, VOL_MIN_G = 2, VOL_MAX_G = 32;
 constexpr int VOL_MAX_ELEMS = 16384;       // V * H * W floats of one LDS image: the product's four 64 x 64 maps
 constexpr int VOL_THREADS = 512, VOL_BWD_THREADS = 1024, VOL_MAX_WAVES = VOL_BWD_THREADS / 64;     // forward, backward workgroup
 
 struct vol_view {          // one per view, in LDS: every lane reads the same address (a broadcast)
-    double R[9], t[3];     // p_cam = R p + t, cm (tri_extrinsics of egr_triangulate.hip)
-    double poly[VOL_MAX_W2C];
+    double R[9], t[3];     // p_cam = R p + t, cm (rays::extrinsics)
+    double poly[rays::MAX_W2C];     // W2C, widened once
     double cx, cy, W_img, H_img;
     double w;              // the view's weight; 0: excluded
     int npoly, pad;
@@ -50,26 +46,12 @@ struct vol_tap {           // one view's sample of one voxel: the LDS index of c
 
 __device__ __forceinline__ void vol_make_view(const float* conf, const float* cams, const float* ctm, int b, int v, int j, int V, int J,
                                               float thr, vol_view& o) {
-    const float* cam = cams + v * VOL_REC;
+    const float* cam = cams + v * rays::REC;
     const float cf = conf[((int64_t)b * V + v) * J + j];
     o.w = (cf >= thr && cf > 0.f && isfinite(cf)) ? (double)cf : 0.0;
-    if (ctm) {
-        const float* m = ctm + ((int64_t)b * V + v) * 16;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) o.R[r * 3 + c] = (double)m[r * 4 + c];
-            o.t[r] = 100.0 * (double)m[r * 4 + 3];
-        }
-    } else {
-        const double fl = cam[VOL_FLIP] != 0.f ? -1.0 : 1.0;
-        for (int i = 0; i < 9; ++i) o.R[i] = 0.0;
-        o.R[0] = fl;
-        o.R[4] = fl;
-        o.R[8] = 1.0;
-        for (int r = 0; r < 3; ++r) o.t[r] = (double)cam[VOL_OFF + r];
-    }
-    int np = (int)cam[0];
-    o.npoly = np < 0 ? 0 : (np > VOL_MAX_W2C ? VOL_MAX_W2C : np);
-    for (int i = 0; i < VOL_MAX_W2C; ++i) o.poly[i] = (double)cam[VOL_W2C + i];
+    rays::extrinsics(cam, ctm, (int64_t)b * V + v, o.R, o.t);
+    o.npoly = rays::w2c_degree(cam);
+    for (int i = 0; i < rays::MAX_W2C; ++i) o.poly[i] = (double)cam[rays::W2C + i];
     o.cx = cam[1];
     o.cy = cam[2];
     o.W_img = cam[3];

@@ -64,9 +64,8 @@ def _check(hm: torch.Tensor, beta: float, mode: int, dims: Optional[int] = None,
     return tuple(hm.shape[:-2]), H, W
 
 
-def _on_device(t: torch.Tensor, what: str):
-    if not t.is_cuda and t.device.type != "meta":
-        raise RuntimeError(f"egorear_amd.decode.{what}: no CPU path - tensors must live on the HIP device")
+def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.contiguous()
 
 
 # ---- the operators ----------------------------------------------------------------------------------------------------------------
@@ -129,7 +128,7 @@ def get_max_preds_soft(batch_heatmaps: torch.Tensor, normalize: bool = False) ->
     """`get_max_preds_soft_pytorch` (utils/loss.py:145-177): batch_heatmaps (B, J, H, W) -> preds (B, J, 2) = softmax-weighted mean
     (x, y) of each map (beta 1; divided by (W, H) with `normalize`), maxvals (B, J, 1) = the maps' maxima.  Both differentiable."""
     _check(batch_heatmaps, 1.0, MODE_SOFTMAX, dims=4, what="get_max_preds_soft")
-    _on_device(batch_heatmaps, "get_max_preds_soft")
+    hip._on_device("decode.get_max_preds_soft", batch_heatmaps)
     coords, maxvals, _, _, _, _ = soft_argmax_op(batch_heatmaps, 1.0, MODE_SOFTMAX, bool(normalize), 0.0, False)
     return coords, maxvals.unsqueeze(-1)
 
@@ -141,7 +140,7 @@ def integrate_tensor_2d(heatmaps: torch.Tensor, softmax: bool = True, multiplier
     NaN there).  The second value is returned detached: gradient flows through the coordinates only."""
     mode = MODE_SOFTMAX if softmax else MODE_RELU
     _check(heatmaps, float(multiplier), mode, dims=4, what="integrate_tensor_2d")
-    _on_device(heatmaps, "integrate_tensor_2d")
+    hip._on_device("decode.integrate_tensor_2d", heatmaps)
     coords, _, _, _, _, probs = soft_argmax_op(heatmaps, float(multiplier), mode, False, 0.0, True)
     return coords, probs.detach()
 
@@ -157,7 +156,7 @@ def decode_joints_2d(heatmaps: torch.Tensor, beta: float = 100.0, threshold: flo
     """heatmaps (B, V, J, H, W) -> Joints2D(soft, hard, maxvals, valid): sub-pixel joints (softmax at `beta`) next to the hard arg-max
     the anchors use, from one read of the maps (one launch; the hard (x, y) are two integer ops on its `index` output)."""
     _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="decode_joints_2d")
-    _on_device(heatmaps, "decode_joints_2d")
+    hip._on_device("decode.decode_joints_2d", heatmaps)
     W = int(heatmaps.shape[-1])
     soft, maxvals, index, valid, _, _ = soft_argmax_op(heatmaps, float(beta), MODE_SOFTMAX, False, float(threshold), False)
     hard = torch.stack((index % W, torch.div(index, W, rounding_mode="floor")), -1).to(torch.float32)
@@ -171,44 +170,18 @@ _PKG_CALIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "calib", "
 _RAY_RECORDS = {}    # (camera_model, calibration directory | the cameras' ids, device) -> (cameras, (V, 30) device tensor)
 
 
-def _check_tri(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
-               min_det_ratio: float, what: str = "triangulate"):
-    if coords.dim() != 4 or coords.shape[-1] != 2:
-        raise ValueError(f"egorear_amd.decode.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
-    B, V, J = (int(v) for v in coords.shape[:3])
-    if not 2 <= V <= 4:
-        raise ValueError(f"egorear_amd.decode.{what}: 2 to 4 views are supported, got {V}")
-    if B < 1 or J < 1:
-        raise ValueError(f"egorear_amd.decode.{what}: empty coords {tuple(coords.shape)}")
-    if tuple(conf.shape) != (B, V, J):
-        raise ValueError(f"egorear_amd.decode.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
-    if tuple(cams.shape) != (V, hip.RAY_REC):
-        raise ValueError(f"egorear_amd.decode.{what}: {V} views need {V} camera records of {hip.RAY_REC} floats, got {tuple(cams.shape)}")
-    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
-        raise ValueError(f"egorear_amd.decode.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
-    for t, name in ((coords, "coords"), (conf, "conf"), (cams, "camera records"), (ctm, "coord_trans_mat")):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"egorear_amd.decode.{what}: float32 {name} expected, got {t.dtype}")
-    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
-        raise ValueError(f"egorear_amd.decode.{what}: heatmap_size must be positive, got scales {(sx, sy)!r}")
-    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
-        raise ValueError(f"egorear_amd.decode.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
-    return B, V, J
-
-
 @torch.library.custom_op("egorear_amd::triangulate", mutates_args=(), device_types="cuda")
 def triangulate_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
                    threshold: float, min_det_ratio: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(pts (B, J, 3) cm, cost (B, J) cm^2, resid (B, V, J) cm, ok (B, J) uint8) of coords (B, V, J, 2) * (sx, sy) = normalised image
     points, conf (B, V, J), cams (V, 30) = camera.packed_rays(), ctm (B, V, 4, 4) or None (the syn rig)."""
-    _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio)
-    return hip.triangulate(coords.contiguous(), conf.contiguous(), cams.contiguous(), None if ctm is None else ctm.contiguous(), sx, sy,
-                           threshold, min_det_ratio)
+    hip._tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "decode.triangulate", dense=False)
+    return hip.triangulate(_c(coords), _c(conf), _c(cams), _c(ctm), sx, sy, threshold, min_det_ratio)
 
 
 @triangulate_op.register_fake
 def _triangulate_fake(coords, conf, cams, ctm, sx, sy, threshold, min_det_ratio):
-    B, V, J = _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio)
+    B, V, J = hip._tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "decode.triangulate", dense=False)
     return (coords.new_empty((B, J, 3)), coords.new_empty((B, J)), coords.new_empty((B, V, J)), coords.new_empty((B, J), dtype=torch.uint8))
 
 
@@ -217,18 +190,15 @@ def triangulate_bwd_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Ten
                        g_pts: Optional[torch.Tensor], g_cost: Optional[torch.Tensor], sx: float, sy: float, threshold: float,
                        min_det_ratio: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """(g_coords (B, V, J, 2), g_conf (B, V, J)) from g_pts (B, J, 3) and g_cost (B, J), each None for zeros."""
-    _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd")
-    gp = None if g_pts is None else g_pts.to(torch.float32).contiguous()
-    gc = None if g_cost is None else g_cost.to(torch.float32).contiguous()
-    return hip.triangulate_bwd(coords.contiguous(), conf.contiguous(), cams.contiguous(), None if ctm is None else ctm.contiguous(), gp, gc,
-                               sx, sy, threshold, min_det_ratio)
+    gp = None if g_pts is None else g_pts.to(torch.float32)
+    gc = None if g_cost is None else g_cost.to(torch.float32)
+    hip._tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "decode.triangulate_bwd", gp, gc, dense=False)
+    return hip.triangulate_bwd(_c(coords), _c(conf), _c(cams), _c(ctm), _c(gp), _c(gc), sx, sy, threshold, min_det_ratio)
 
 
 @triangulate_bwd_op.register_fake
 def _triangulate_bwd_fake(coords, conf, cams, ctm, g_pts, g_cost, sx, sy, threshold, min_det_ratio):
-    B, V, J = _check_tri(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd")
-    if (g_pts is not None and tuple(g_pts.shape) != (B, J, 3)) or (g_cost is not None and tuple(g_cost.shape) != (B, J)):
-        raise ValueError(f"egorear_amd.decode.triangulate_bwd: g_pts must be {(B, J, 3)} and g_cost {(B, J)}")
+    B, V, J = hip._tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "decode.triangulate_bwd", g_pts, g_cost, dense=False)
     return coords.new_empty((B, V, J, 2)), coords.new_empty((B, V, J))
 
 
@@ -303,15 +273,9 @@ def triangulate_joints(coords: torch.Tensor, conf: torch.Tensor, cameras: Union[
     not chain); with it (B, V, 4, 4), device frame (m) -> camera frame as in the rw models.  One launch; pose and cost are
     differentiable with respect to coords and conf."""
     sx, sy = _scales(heatmap_size)
-    if not (float(min_det_ratio) >= 0.0 and math.isfinite(float(min_det_ratio))):
-        raise ValueError(f"egorear_amd.decode.triangulate_joints: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
-    if coords.dim() != 4 or not 2 <= coords.shape[1] <= 4:
-        raise ValueError(f"egorear_amd.decode.triangulate_joints: coords must be (B, V, J, 2) with 2 to 4 views, got {tuple(coords.shape)}")
     cams = _ray_records(cameras, camera_calib_file_dir_path, coords.device)
-    _check_tri(coords, conf, cams, coord_trans_mat, sx, sy, float(min_det_ratio), "triangulate_joints")
-    for t in (coords, conf, coord_trans_mat):
-        if t is not None:
-            _on_device(t, "triangulate_joints")
+    hip._tri_operands(coords, conf, cams, coord_trans_mat, sx, sy, float(min_det_ratio), "decode.triangulate_joints", dense=False)
+    hip._on_device("decode.triangulate_joints", coords, conf, coord_trans_mat)
     pts, cost, resid, ok = triangulate_op(coords, conf, cams, coord_trans_mat, sx, sy, float(threshold), float(min_det_ratio))
     return Joints3D(pts, cost, resid, ok.view(torch.bool))
 
@@ -323,7 +287,7 @@ def decode_joints_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coor
     maps' maxima - two launches with nothing between them (the pixel scale and the threshold are kernel arguments).  Gradients of
     pose and cost reach the heat maps through both backward operators."""
     _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="decode_joints_3d")
-    if not 2 <= heatmaps.shape[1] <= 4:
+    if not 2 <= heatmaps.shape[1] <= 4:      # (the soft-argmax takes any V: without this it would run before the triangulation refuses)
         raise ValueError(f"egorear_amd.decode.decode_joints_3d: 2 to 4 views are supported, got {tuple(heatmaps.shape)}")
     joints2d = decode_joints_2d(heatmaps, beta=beta, threshold=threshold)
     H, W = int(heatmaps.shape[-2]), int(heatmaps.shape[-1])
@@ -337,10 +301,6 @@ def decode_joints_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coor
 def _check_vol(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, what: str = "volume_fuse", g_pose=None, g_peak=None):
     # (the operators make their operands contiguous before the launch, which checks that too)
     return hip._volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "decode." + what, g_pose, g_peak, dense=False)
-
-
-def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    return None if t is None else t.contiguous()
 
 
 @torch.library.custom_op("egorear_amd::volume_fuse", mutates_args=(), device_types="cuda")
@@ -418,9 +378,7 @@ def _fuse(heatmaps, centers, cams, conf, coord_trans_mat, center_ok, grid, cube_
     if isinstance(grid, bool) or not isinstance(grid, int):
         raise ValueError(f"egorear_amd.decode.{what}: grid must be an integer, got {grid!r}")
     _check_vol(heatmaps, conf, centers, cams, coord_trans_mat, center_ok, grid, float(cube_cm), float(beta), what)
-    for t in (heatmaps, conf, centers, coord_trans_mat, center_ok):
-        if t is not None:
-            _on_device(t, what)
+    hip._on_device("decode." + what, heatmaps, conf, centers, coord_trans_mat, center_ok)
     pose, peak, index, spread, ok = volume_fuse_op(heatmaps, conf, centers, cams, coord_trans_mat, center_ok, grid, float(cube_cm),
                                                    float(beta), float(threshold))
     return Volume3D(pose, peak, index, spread, ok.view(torch.bool))
@@ -436,8 +394,6 @@ def fuse_joints_volumetric(heatmaps: torch.Tensor, centers: torch.Tensor, camera
     mean voxel.  `cameras` and `coord_trans_mat` as in `triangulate_joints`.  The centres come from `decode_joints_3d` or from a
     lifting head's pose; they and `conf` are constants - pose and peak are differentiable with respect to the heat maps, of all views
     jointly.  One launch (V * H * W <= 16384, 2 <= grid <= 32)."""
-    if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
-        raise ValueError(f"egorear_amd.decode.fuse_joints_volumetric: heat maps must be (B, V, J, H, W) with 2 to 4 views, got {tuple(heatmaps.shape)}")
     cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
     return _fuse(heatmaps, centers, cams, conf, coord_trans_mat, None, grid, cube_cm, beta, threshold, "fuse_joints_volumetric")
 
@@ -451,9 +407,6 @@ def decode_joints_3d_volumetric(heatmaps: torch.Tensor, cameras: Union[str, Sequ
     launches with no torch arithmetic between them.  A joint whose triangulation is not valid is not valid here.  The gradient of the
     fused pose and peak reaches the heat maps through the fusion alone (the cube is placed, not learned); the triangulated pose and
     cost keep their own gradients."""
-    _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="decode_joints_3d_volumetric")
-    if not 2 <= heatmaps.shape[1] <= 4:
-        raise ValueError(f"egorear_amd.decode.decode_joints_3d_volumetric: 2 to 4 views are supported, got {tuple(heatmaps.shape)}")
     joints3d, joints2d = decode_joints_3d(heatmaps, cameras, coord_trans_mat, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
     cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
     # (bool -> uint8 and detach are reinterpretations: nothing is launched for them)
@@ -463,12 +416,6 @@ def decode_joints_3d_volumetric(heatmaps: torch.Tensor, cameras: Union[str, Sequ
 
 
 # ---- multi-peak decoding and consensus triangulation --------------------------------------------------------------------------------
-
-def _refuse_cpu(what: str, *tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda and t.device.type != "meta":
-            raise ValueError(f"egorear_amd.decode.{what}: no CPU path - tensors must live on the HIP device")
-
 
 @torch.library.custom_op("egorear_amd::find_peaks", mutates_args=(), device_types="cuda")
 def find_peaks_op(hm: torch.Tensor, k: int, nms_radius: int, refine_radius: int, beta: float, threshold: float
@@ -544,7 +491,7 @@ def find_peaks_2d(heatmaps: torch.Tensor, k: int = 3, nms_radius: int = 1, refin
     if heatmaps.dim() != 5:
         raise ValueError(f"egorear_amd.decode.find_peaks_2d: heat maps must be (B, V, J, H, W), got {tuple(heatmaps.shape)}")
     hip._peaks_operands(heatmaps, k, nms_radius, refine_radius, float(beta), float(threshold), "decode.find_peaks_2d", dense=False)
-    _refuse_cpu("find_peaks_2d", heatmaps)
+    hip._on_device("decode.find_peaks_2d", heatmaps, exc=ValueError)
     return Peaks2D(*find_peaks_op(heatmaps, k, nms_radius, refine_radius, float(beta), float(threshold)))
 
 
@@ -558,12 +505,10 @@ def select_consistent(peaks: Peaks2D, cameras: Union[str, Sequence], coord_trans
     `triangulate_joints` takes.  `cameras` and `coord_trans_mat` as there.  One launch.  Nothing here is differentiable."""
     sx, sy = _scales(heatmap_size)
     cand, cscore, cindex = peaks[0], peaks[1], peaks[2]
-    if cand.dim() != 5 or not 2 <= cand.shape[1] <= 4:
-        raise ValueError(f"egorear_amd.decode.select_consistent: candidates must be (B, V, J, K, 2) with 2 to 4 views, got {tuple(cand.shape)}")
     cams = _ray_records(cameras, camera_calib_file_dir_path, cand.device)
     hip._consensus_operands(cand, cscore, cindex, cams, coord_trans_mat, sx, sy, float(max_reproj), min_views, float(min_det_ratio),
                             "decode.select_consistent", dense=False)
-    _refuse_cpu("select_consistent", cand, cscore, cindex, coord_trans_mat)
+    hip._on_device("decode.select_consistent", cand, cscore, cindex, coord_trans_mat, exc=ValueError)
     choice, sel_coords, sel_conf, score, inliers, hyp = consensus_op(cand, cscore, cindex, cams, coord_trans_mat, sx, sy, float(max_reproj),
                                                                      min_views, float(min_det_ratio))
     return Consensus(sel_coords, sel_conf, choice, score, inliers, hyp)
@@ -578,6 +523,7 @@ def decode_joints_3d_robust(heatmaps: torch.Tensor, cameras: Union[str, Sequence
     triangulation's operands).  A view whose map fired on a second mode is out-voted by the others instead of bending the pose;
     `Joints3D.residual` reports the accepted views only, and a joint without a consensus is not valid.  With two views there is no
     third to out-vote a distractor: the consensus then only rejects pairs that do not meet.  Nothing here is differentiable."""
+    # (the peaks take any V: without this guard they would run before the consensus refuses)
     if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
         raise ValueError(f"egorear_amd.decode.decode_joints_3d_robust: heat maps must be (B, V, J, H, W) with 2 to 4 views, got "
                          f"{tuple(heatmaps.shape)}")

@@ -8,6 +8,7 @@ entry point.  There is no fallback: if the library is missing, import fails loud
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from typing import Optional, Union
@@ -1273,40 +1274,71 @@ def coord_l1(coords: torch.Tensor, index: torch.Tensor, valid: torch.Tensor, wid
     return g
 
 
-RAY_REC = 30      # floats of one camera.packed_rays() record
+RAY_REC = 30      # floats of one camera.packed_rays() record (its layout: csrc/egr_rays.h)
 
 
-def _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, what: str, g_pts=None, g_cost=None):
-    """(B, V, J) of a triangulation launch; every shape / dtype / parameter error as ValueError, then the device."""
-    import math
-    if coords.dim() != 4 or coords.shape[-1] != 2:
-        raise ValueError(f"egorear_amd.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
-    B, V, J = (int(v) for v in coords.shape[:3])
+# what the validators of the launches on ray records share; `named` are (tensor | None, name) pairs
+
+def _on_device(what: str, *tensors, exc=RuntimeError):
+    """There is no CPU path.  (Meta tensors pass: the fake implementations and a trace validate with them.)"""
+    for t in tensors:
+        if t is not None and not t.is_cuda and t.device.type != "meta":
+            raise exc(f"egorear_amd.{what}: no CPU path - tensors must live on the HIP device")
+
+
+def _rig(what: str, cams, ctm, B: int, V: int):
     if not 2 <= V <= 4:
         raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
-    if B < 1 or J < 1:
-        raise ValueError(f"egorear_amd.{what}: empty coords {tuple(coords.shape)}")
-    if tuple(conf.shape) != (B, V, J):
-        raise ValueError(f"egorear_amd.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
     if tuple(cams.shape) != (V, RAY_REC):
         raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
     if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
         raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
-    for t, name in ((coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat")):
+
+
+def _float32(what: str, *named):
+    for t, name in named:
         if t is not None and t.dtype != torch.float32:
             raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
-        if t is not None and not t.is_contiguous():
+
+
+def _cotangents(what: str, *specs):
+    for t, shape, name in specs:
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
+            raise ValueError(f"egorear_amd.{what}: {name} must be a float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _contiguous(what: str, dense: bool, *named):
+    # (dense: a launch reads its operands as they lie; the operators validate first and make them contiguous after)
+    for t, name in named:
+        if dense and t is not None and not t.is_contiguous():
             raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
-    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
-        raise ValueError(f"egorear_amd.{what}: the coordinate scales must be positive and finite, got {(sx, sy)!r}")
-    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
-        raise ValueError(f"egorear_amd.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
-    for t, shape, name in ((g_pts, (B, J, 3), "g_pts"), (g_cost, (B, J), "g_cost")):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"egorear_amd.{what}: {name} must be a contiguous float32 {shape}, got {t.dtype} {tuple(t.shape)}")
-    for t in (coords, conf, cams, ctm, g_pts, g_cost):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"egorear_amd.{what}: no CPU path - tensors must live on the HIP device")
+
+
+def _positive(what: str, name: str, *values):
+    if not all(v > 0.0 and math.isfinite(v) for v in values):
+        raise ValueError(f"egorear_amd.{what}: {name} must be positive and finite, got {values!r}")
+
+
+def _non_negative(what: str, name: str, value):
+    if not (value >= 0.0 and math.isfinite(value)):
+        raise ValueError(f"egorear_amd.{what}: {name} must be a non-negative finite number, got {value!r}")
+
+
+def _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, what: str, g_pts=None, g_cost=None, dense: bool = True):
+    """(B, V, J) of a triangulation launch; every shape / dtype / parameter error as ValueError."""
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    B, V, J = (int(v) for v in coords.shape[:3])
+    if B < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty coords {tuple(coords.shape)}")
+    if tuple(conf.shape) != (B, V, J):
+        raise ValueError(f"egorear_amd.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
+    _rig(what, cams, ctm, B, V)
+    _float32(what, (coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    _positive(what, "the coordinate scales", sx, sy)
+    _non_negative(what, "min_det_ratio", min_det_ratio)
+    _cotangents(what, (g_pts, (B, J, 3), "g_pts"), (g_cost, (B, J), "g_cost"))
+    _contiguous(what, dense, (coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"), (g_pts, "g_pts"), (g_cost, "g_cost"))
     return B, V, J
 
 
@@ -1315,6 +1347,7 @@ def triangulate(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ct
     """coords (B,V,J,2), conf (B,V,J), cams (V,30) = camera.packed_rays(), ctm (B,V,4,4) | None (the syn rig) -> pts (B,J,3) cm,
     cost (B,J) cm^2, resid (B,V,J) cm, ok (B,J) u8: egr_triangulate_f32, the least-squares intersection of the views' fisheye rays."""
     B, V, J = _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate")
+    _on_device("triangulate", coords, conf, cams, ctm)
     dev = coords.device
     pts = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
     cost = torch.empty((B, J), device=dev, dtype=torch.float32)
@@ -1331,6 +1364,7 @@ def triangulate_bwd(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor
     """Gradients of triangulate's pts and cost with respect to coords and conf, (B,V,J,2) and (B,V,J): egr_triangulate_bwd_f32 (the
     forward is recomputed from the operands).  g_pts (B,J,3) and g_cost (B,J) may each be None for zeros."""
     B, V, J = _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, "triangulate_bwd", g_pts, g_cost)
+    _on_device("triangulate_bwd", coords, conf, cams, ctm, g_pts, g_cost)
     dev = coords.device
     g_coords = torch.empty((B, V, J, 2), device=dev, dtype=torch.float32)
     g_conf = torch.empty((B, V, J), device=dev, dtype=torch.float32)
@@ -1347,50 +1381,30 @@ VOLUME_MIN_GRID, VOLUME_MAX_GRID = 2, 32
 def _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, what: str, g_pose=None, g_peak=None, dense: bool = True):
     """(B, V, J, H, W) of a volumetric-fusion launch; every shape / dtype / parameter error as ValueError (dense: the operands must
     be contiguous too - a launch reads them as they lie)."""
-    import math
     if hm.dim() != 5:
         raise ValueError(f"egorear_amd.{what}: heat maps must be (B, V, J, H, W), got {tuple(hm.shape)}")
     B, V, J, H, W = (int(v) for v in hm.shape)
-    if not 2 <= V <= 4:
-        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
     if B < 1 or J < 1 or H < 1 or W < 1:
         raise ValueError(f"egorear_amd.{what}: empty heat maps {tuple(hm.shape)}")
+    _rig(what, cams, ctm, B, V)
     if V * H * W > VOLUME_MAX_ELEMS:
         raise ValueError(f"egorear_amd.{what}: the V * H * W = {V * H * W} elements of a joint's maps exceed the {VOLUME_MAX_ELEMS} the "
                          f"kernel holds in LDS")
     if isinstance(grid, bool) or not isinstance(grid, int) or not VOLUME_MIN_GRID <= grid <= VOLUME_MAX_GRID:
         raise ValueError(f"egorear_amd.{what}: grid must be an integer in {VOLUME_MIN_GRID}..{VOLUME_MAX_GRID}, got {grid!r}")
-    if not (cube > 0.0 and math.isfinite(cube)):
-        raise ValueError(f"egorear_amd.{what}: the cube's side must be a positive finite number of cm, got {cube!r}")
-    if not (beta > 0.0 and math.isfinite(beta)):
-        raise ValueError(f"egorear_amd.{what}: beta must be a positive finite number, got {beta!r}")
+    _positive(what, "the cube's side (cm)", cube)
+    _positive(what, "beta", beta)
     if tuple(conf.shape) != (B, V, J):
         raise ValueError(f"egorear_amd.{what}: conf must be {(B, V, J)}, got {tuple(conf.shape)}")
     if tuple(centers.shape) != (B, J, 3):
         raise ValueError(f"egorear_amd.{what}: centers must be {(B, J, 3)}, got {tuple(centers.shape)}")
-    if tuple(cams.shape) != (V, RAY_REC):
-        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
-    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
-        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
     if center_ok is not None and (tuple(center_ok.shape) != (B, J) or center_ok.dtype != torch.uint8):
         raise ValueError(f"egorear_amd.{what}: center_ok must be a uint8 {(B, J)}, got {center_ok.dtype} {tuple(center_ok.shape)}")
-    for t, name in ((hm, "heat maps"), (conf, "conf"), (centers, "centers"), (cams, "cams"), (ctm, "coord_trans_mat")):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
-    for t, shape, name in ((g_pose, (B, J, 3), "g_pose"), (g_peak, (B, J), "g_peak")):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
-            raise ValueError(f"egorear_amd.{what}: {name} must be a float32 {shape}, got {t.dtype} {tuple(t.shape)}")
-    for t, name in ((hm, "heat maps"), (conf, "conf"), (centers, "centers"), (cams, "cams"), (ctm, "coord_trans_mat"),
-                    (center_ok, "center_ok"), (g_pose, "g_pose"), (g_peak, "g_peak")):
-        if dense and t is not None and not t.is_contiguous():
-            raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
+    floats = ((hm, "heat maps"), (conf, "conf"), (centers, "centers"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    _float32(what, *floats)
+    _cotangents(what, (g_pose, (B, J, 3), "g_pose"), (g_peak, (B, J), "g_peak"))
+    _contiguous(what, dense, *floats, (center_ok, "center_ok"), (g_pose, "g_pose"), (g_peak, "g_peak"))
     return B, V, J, H, W
-
-
-def _volume_on_device(what: str, *tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"egorear_amd.{what}: no CPU path - tensors must live on the HIP device")
 
 
 def volume_fuse(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None,
@@ -1399,7 +1413,7 @@ def volume_fuse(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor, cam
     center_ok (B,J) u8 | None -> pose (B,J,3) cm, peak (B,J), index (B,J) i32, spread (B,J) cm, ok (B,J) u8: egr_volume_fuse_f32, the
     3-D soft-argmax of the views' heat maps sampled at the projections of a grid^3 voxel cube of side `cube` around each centre."""
     B, V, J, H, W = _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse")
-    _volume_on_device("volume_fuse", hm, conf, centers, cams, ctm, center_ok)
+    _on_device("volume_fuse", hm, conf, centers, cams, ctm, center_ok)
     dev = hm.device
     pose = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
     peak = torch.empty((B, J), device=dev, dtype=torch.float32)
@@ -1418,7 +1432,7 @@ def volume_fuse_bwd(hm: torch.Tensor, conf: torch.Tensor, centers: torch.Tensor,
     """Gradient of volume_fuse's pose and peak with respect to hm, (B,V,J,H,W): egr_volume_fuse_bwd_f32 (the forward is recomputed
     from the operands; every element is written).  g_pose (B,J,3) and g_peak (B,J) may each be None for zeros."""
     B, V, J, H, W = _volume_operands(hm, conf, centers, cams, ctm, center_ok, grid, cube, beta, "volume_fuse_bwd", g_pose, g_peak)
-    _volume_on_device("volume_fuse_bwd", hm, conf, centers, cams, ctm, center_ok, g_pose, g_peak)
+    _on_device("volume_fuse_bwd", hm, conf, centers, cams, ctm, center_ok, g_pose, g_peak)
     g_hm = torch.empty((B, V, J, H, W), device=hm.device, dtype=torch.float32)
     _launch("egr_volume_fuse_bwd_f32", lib.egr_volume_fuse_bwd_f32, _p(hm), _p(conf), _p(centers), _p(cams), _p(ctm),
             _p(center_ok, torch.uint8), B, V, J, H, W, int(grid), float(cube), float(beta), float(threshold), _p(g_pose), _p(g_peak),
@@ -1436,7 +1450,6 @@ def _int_in(v, lo: int, hi: int) -> bool:
 
 def _peaks_operands(hm, k, nms_radius, refine_radius, beta, min_score, what: str, dense: bool = True):
     """(lead shape, rows, H, W) of a peaks launch over (..., H, W) maps; every shape / dtype / parameter error as ValueError."""
-    import math
     if hm.dim() < 2:
         raise ValueError(f"egorear_amd.{what}: heat maps must be (..., H, W), got {tuple(hm.shape)}")
     if hm.dtype != torch.float32:
@@ -1450,12 +1463,10 @@ def _peaks_operands(hm, k, nms_radius, refine_radius, beta, min_score, what: str
         raise ValueError(f"egorear_amd.{what}: nms_radius must be an integer in 1..{PEAKS_MAX_NMS}, got {nms_radius!r}")
     if not _int_in(refine_radius, 0, PEAKS_MAX_REFINE):
         raise ValueError(f"egorear_amd.{what}: refine_radius must be an integer in 0..{PEAKS_MAX_REFINE}, got {refine_radius!r}")
-    if not (beta > 0.0 and math.isfinite(beta)):
-        raise ValueError(f"egorear_amd.{what}: beta must be a positive finite number, got {beta!r}")
+    _positive(what, "beta", beta)
     if not math.isfinite(min_score):
         raise ValueError(f"egorear_amd.{what}: the score threshold must be finite, got {min_score!r}")
-    if dense and not hm.is_contiguous():
-        raise ValueError(f"egorear_amd.{what}: heat maps must be contiguous")
+    _contiguous(what, dense, (hm, "heat maps"))
     return tuple(hm.shape[:-2]), hm.numel() // (H * W), H, W
 
 
@@ -1464,7 +1475,7 @@ def find_peaks(hm: torch.Tensor, k: int = 3, nms_radius: int = 1, refine_radius:
     count (rows,) i32: egr_peaks_f32, the k best local maxima of every map (value, then smaller flat index), each refined over its
     (2 refine_radius + 1)^2 window.  Slots past count: coords 0, score 0, index -1."""
     _, rows, H, W = _peaks_operands(hm, k, nms_radius, refine_radius, beta, min_score, "find_peaks")
-    _volume_on_device("find_peaks", hm)
+    _on_device("find_peaks", hm)
     dev = hm.device
     coords = torch.empty((rows, k, 2), device=dev, dtype=torch.float32)
     score = torch.empty((rows, k), device=dev, dtype=torch.float32)
@@ -1477,38 +1488,26 @@ def find_peaks(hm: torch.Tensor, k: int = 3, nms_radius: int = 1, refine_radius:
 
 def _consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, what: str, dense: bool = True):
     """(B, V, J, K) of a consensus launch; every shape / dtype / parameter error as ValueError."""
-    import math
     if cand.dim() != 5 or cand.shape[-1] != 2:
         raise ValueError(f"egorear_amd.{what}: candidates must be (B, V, J, K, 2), got {tuple(cand.shape)}")
     B, V, J, K = (int(v) for v in cand.shape[:4])
-    if not 2 <= V <= 4:
-        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
     if not 1 <= K <= PEAKS_MAX_K:
         raise ValueError(f"egorear_amd.{what}: 1 to {PEAKS_MAX_K} candidates per view are supported, got {K}")
     if B < 1 or J < 1:
         raise ValueError(f"egorear_amd.{what}: empty candidates {tuple(cand.shape)}")
     if tuple(cscore.shape) != (B, V, J, K) or tuple(cindex.shape) != (B, V, J, K):
         raise ValueError(f"egorear_amd.{what}: scores and indices must be {(B, V, J, K)}, got {tuple(cscore.shape)} and {tuple(cindex.shape)}")
-    if tuple(cams.shape) != (V, RAY_REC):
-        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
-    if ctm is not None and tuple(ctm.shape) != (B, V, 4, 4):
-        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(B, V, 4, 4)}, got {tuple(ctm.shape)}")
-    for t, name in ((cand, "candidates"), (cscore, "scores"), (cams, "cams"), (ctm, "coord_trans_mat")):
-        if t is not None and t.dtype != torch.float32:
-            raise ValueError(f"egorear_amd.{what}: float32 {name} expected, got {t.dtype}")
+    _rig(what, cams, ctm, B, V)
+    floats = ((cand, "candidates"), (cscore, "scores"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    _float32(what, *floats)
     if cindex.dtype != torch.int32:
         raise ValueError(f"egorear_amd.{what}: int32 indices expected, got {cindex.dtype}")
-    if not (sx > 0.0 and sy > 0.0 and math.isfinite(sx) and math.isfinite(sy)):
-        raise ValueError(f"egorear_amd.{what}: the coordinate scales must be positive and finite, got {(sx, sy)!r}")
-    if not (max_reproj > 0.0 and math.isfinite(max_reproj)):
-        raise ValueError(f"egorear_amd.{what}: max_reproj must be a positive finite number, got {max_reproj!r}")
+    _positive(what, "the coordinate scales", sx, sy)
+    _positive(what, "max_reproj", max_reproj)
     if not _int_in(min_views, 2, V):
         raise ValueError(f"egorear_amd.{what}: min_views must be an integer in 2..{V}, got {min_views!r}")
-    if not (min_det_ratio >= 0.0 and math.isfinite(min_det_ratio)):
-        raise ValueError(f"egorear_amd.{what}: min_det_ratio must be a non-negative finite number, got {min_det_ratio!r}")
-    for t, name in ((cand, "candidates"), (cscore, "scores"), (cindex, "indices"), (cams, "cams"), (ctm, "coord_trans_mat")):
-        if dense and t is not None and not t.is_contiguous():
-            raise ValueError(f"egorear_amd.{what}: {name} must be contiguous")
+    _non_negative(what, "min_det_ratio", min_det_ratio)
+    _contiguous(what, dense, *floats, (cindex, "indices"))
     return B, V, J, K
 
 
@@ -1518,7 +1517,7 @@ def consensus(cand: torch.Tensor, cscore: torch.Tensor, cindex: torch.Tensor, ca
     i32, sel_coords (B,V,J,2), sel_conf (B,V,J), score (B,J), inliers (B,J) i32, hyp (B,J) i32: egr_consensus_f32, per joint the
     candidates the views agree on - the two-view hypothesis whose reprojections the views' candidates support best."""
     B, V, J, K = _consensus_operands(cand, cscore, cindex, cams, ctm, sx, sy, max_reproj, min_views, min_det_ratio, "consensus")
-    _volume_on_device("consensus", cand, cscore, cindex, cams, ctm)
+    _on_device("consensus", cand, cscore, cindex, cams, ctm)
     dev = cand.device
     choice = torch.empty((B, V, J), device=dev, dtype=torch.int32)
     sel_coords = torch.empty((B, V, J, 2), device=dev, dtype=torch.float32)

@@ -155,6 +155,64 @@ def test_the_entry_refuses_what_it_does_not_support():
         assert rc == hip.EINVAL, (change, rc)
 
 
+# --------------------------------------------------------------------------- the consensus point is the triangulated point
+
+def support(p, cand, cscore, cindex, rec, ctm):
+    """RS.consensus_statement's support of the points p (B, J, 3), in p's dtype: (score (B, J), inliers (B, J) int32)."""
+    exists = RS.candidates_exist(cand, cscore, cindex)
+    zero = torch.zeros_like(cscore)
+    xy = torch.where(exists.unsqueeze(-1), cand, torch.zeros_like(cand))
+    proj = RS.project_to(p, rec, None if ctm is None else ctm.to(p.dtype), 1.0 / HM, 1.0 / HM)
+    keep = 1.0 - ((proj.unsqueeze(3) - xy) ** 2).sum(-1) / (TAU * TAU)
+    best = torch.where(exists & (keep > 0), torch.where(exists, cscore, zero) * keep, zero).max(-1)[0]      # (B, V, J): 0 = no support
+    return best.sum(1), (best > 0).sum(1).to(torch.int32)
+
+
+# (B, V, J, K, rw): one hypothesis a pair; 96 of them, two passes over the 64 lanes
+SHARED = [(2, 2, 3, 1, False), (2, 2, 3, 1, True), (2, 4, 3, 4, False), (2, 4, 3, 4, True)]
+
+
+@pytest.mark.parametrize("shape", SHARED)
+def test_the_winning_hypothesis_scores_what_its_triangulated_point_scores(shape):
+    """The consensus solves its two rays with the triangulation's code (egr_rays.h): egr_triangulate_f32 of the winning hypothesis's
+    two candidates gives the point whose reprojections, in float64 on the host, support the candidates with the kernel's `score`
+    (the yardstick of test_consensus_against_the_float64_statement) and in exactly the kernel's `inliers` views."""
+    from egorear_amd import hip
+    B, V, J, K, rw = shape
+    g = torch.Generator().manual_seed(7000 + 100 * V + 10 * K + int(rw))
+    cams = TT.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
+    rec = TT.records(cams)
+    ctm = TT.random_ctm(B, V, cams, g) if rw else None
+    true = (TT.project(TT.random_points(B, J, g), rec, ctm) * HM).float()
+    cand, cscore, cindex, mv = make_case("projected", shape, g, true)
+    assert float(cscore.min()) >= TT.THR                                               # every candidate's view counts in the triangulation
+    f64 = RS.consensus_statement(cand.double(), cscore.double(), cindex, rec, ctm, 1.0 / HM, 1.0 / HM, TAU, mv)
+    f32 = RS.consensus_statement(cand, cscore, cindex, rec, ctm, 1.0 / HM, 1.0 / HM, TAU, mv)
+    sure = RS.decided(f64)
+    assert int((~sure).sum()) * 20 <= B * J and bool((f64["hyp"] >= 0).all()), shape     # on the statement alone
+    d = {"rec": rec, "ctm": ctm}
+    _, _, _, score, inliers, hyp = (t.cpu() for t in launch(d, cand, cscore, cindex, mv))
+    assert torch.equal(hyp[sure], f64["hyp"][sure]) and torch.equal(inliers[sure], f64["inliers"][sure]), shape
+    assert bool((hyp >= 0).all())
+    # the winning hypothesis's two candidates, every other view excluded by a confidence of 0
+    coords, conf = torch.zeros(B, V, J, 2), torch.zeros(B, V, J)
+    pairs = RS.view_pairs(V)
+    for b in range(B):
+        for j in range(J):
+            h = int(hyp[b, j])
+            (va, vb), ka, kb = pairs[h // (K * K)], (h // K) % K, h % K
+            for v, k in ((va, ka), (vb, kb)):
+                coords[b, v, j], conf[b, v, j] = cand[b, v, j, k], cscore[b, v, j, k]
+    pts, _, _, ok = (t.cpu() for t in TT.launch(d, coords, conf))
+    assert bool(ok.all()), shape
+    want, views = support(pts.double(), cand.double(), cscore.double(), cindex, rec, ctm)
+    print(f"{shape}: hypotheses {sorted(set(hyp.view(-1).tolist()))}, inliers {sorted(set(inliers.view(-1).tolist()))}")
+    assert torch.equal(inliers, views), shape
+    own = f32["all_score"].gather(2, f64["hyp"].long().unsqueeze(-1)).squeeze(-1)
+    err, allowed = TT.yardstick("score", score[sure], own[sure], want[sure])
+    assert err <= allowed, (shape, err, allowed)
+
+
 # --------------------------------------------------------------------------- heat maps to 3-D, robustly
 
 @pytest.fixture(scope="module")
