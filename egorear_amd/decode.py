@@ -26,6 +26,12 @@ candidates the views agree on - every two-view pair of candidates is triangulate
 support its reprojections - on `egr_peaks_f32` / `egr_consensus_f32` (DESIGN.md 5p), operators `egorear_amd::find_peaks`,
 `egorear_amd::consensus`, neither differentiable - and `decode_joints_3d_robust` chains three launches: heat maps -> Peaks2D ->
 Consensus -> Joints3D of the accepted views, so that one view firing on a second mode is out-voted instead of bending the pose.
+
+`fit_skeleton` treats the joints of a frame as a skeleton: the rays' distances plus a bone-length term along the kinematic tree plus
+an optional prior, minimised by Levenberg-Marquardt on `egr_skeleton_fit_f32` (DESIGN.md 5q), operator `egorear_amd::skeleton_fit` - a
+joint only one camera sees is placed by its ray and its bone.  `estimate_bone_lengths` (`egorear_amd::bone_lengths`) measures the bones
+of a clip, `resize_skeleton` (`egorear_amd::skeleton_resize`) is the reference's rescale along the chain, and
+`decode_joints_3d_skeleton` chains heat maps -> Joints2D -> Joints3D -> Skeleton3D.  None of them is differentiable.
 """
 from __future__ import annotations
 
@@ -534,3 +540,200 @@ def decode_joints_3d_robust(heatmaps: torch.Tensor, cameras: Union[str, Sequence
     joints3d = triangulate_joints(agreed.coords, agreed.conf, cameras, coord_trans_mat, (H, W), threshold, min_det_ratio,
                                   camera_calib_file_dir_path)
     return joints3d, agreed, peaks
+
+
+# ---- bone-length-constrained skeleton fit -------------------------------------------------------------------------------------------
+
+# Skeleton.kinematic_parents (pose_estimation/utils/skeleton.py:33-34) over the 16 joints of its heatmap_sequence: head, neck, then the
+# arms and the legs down to the balls of the feet
+SKELETON_PARENTS_16 = (0, 0, 1, 1, 2, 3, 4, 5, 2, 3, 8, 9, 10, 11, 12, 13)
+# the 15 heat-map joints: the same tree without the head, re-indexed - the neck is the root
+HEATMAP_PARENTS_15 = (0, 0, 0, 1, 2, 3, 4, 1, 2, 7, 8, 9, 10, 11, 12)
+
+
+def _parents_for(parents, J: int, what: str):
+    """The caller's table as it is (hip's validators judge it), or the 16- / 15-joint table by J."""
+    if parents is not None:
+        return parents
+    if J == 16:
+        return list(SKELETON_PARENTS_16)
+    if J == 15:
+        return list(HEATMAP_PARENTS_15)
+    raise ValueError(f"egorear_amd.decode.{what}: {J} joints need an explicit parent table (15 and 16 have one)")
+
+
+@torch.library.custom_op("egorear_amd::skeleton_fit", mutates_args=(), device_types="cuda")
+def skeleton_fit_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], parents: Sequence[int],
+                    bone_length: torch.Tensor, init: torch.Tensor, init_ok: torch.Tensor, sx: float, sy: float, threshold: float,
+                    min_det_ratio: float, bone_weight: float, prior_weight: float, iterations: int
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose (B, J, 3) cm, ray_cost (B, J), bone (B, J), valid (B, J) uint8, energy0 (B), energy (B), grad (B), steps (B) int32) of the
+    triangulation's operands, a parent table, bone_length (J) or (B, J), init (B, J, 3) and init_ok (B, J) uint8: egr_skeleton_fit_f32
+    (DESIGN.md 5q).  No output is differentiable: the implicit-function backward is not part of this operator."""
+    hip._skeleton_operands(coords, conf, cams, ctm, parents, bone_length, init, init_ok, sx, sy, min_det_ratio, bone_weight, prior_weight,
+                           iterations, "decode.skeleton_fit", dense=False)
+    return hip.skeleton_fit(_c(coords), _c(conf), _c(cams), _c(ctm), parents, _c(bone_length), _c(init), _c(init_ok), sx, sy, threshold,
+                            min_det_ratio, bone_weight, prior_weight, iterations)
+
+
+@skeleton_fit_op.register_fake
+def _skeleton_fit_fake(coords, conf, cams, ctm, parents, bone_length, init, init_ok, sx, sy, threshold, min_det_ratio, bone_weight,
+                       prior_weight, iterations):
+    B, V, J, _, _ = hip._skeleton_operands(coords, conf, cams, ctm, parents, bone_length, init, init_ok, sx, sy, min_det_ratio, bone_weight,
+                                           prior_weight, iterations, "decode.skeleton_fit", dense=False)
+    new = coords.new_empty
+    return (new((B, J, 3)), new((B, J)), new((B, J)), new((B, J), dtype=torch.uint8), new((B,)), new((B,)), new((B,)),
+            new((B,), dtype=torch.int32))
+
+
+@torch.library.custom_op("egorear_amd::bone_lengths", mutates_args=(), device_types="cuda")
+def bone_lengths_op(pose: torch.Tensor, valid: torch.Tensor, parents: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(length (J), spread (J), count (J) int32) of pose (B, J, 3), valid (B, J) uint8: egr_bone_lengths_f32.  Not differentiable."""
+    hip._pose_operands(pose, valid, parents, "decode.bone_lengths", dense=False)
+    return hip.bone_lengths(_c(pose), _c(valid), parents)
+
+
+@bone_lengths_op.register_fake
+def _bone_lengths_fake(pose, valid, parents):
+    _, J, _ = hip._pose_operands(pose, valid, parents, "decode.bone_lengths", dense=False)
+    return pose.new_empty((J,)), pose.new_empty((J,)), pose.new_empty((J,), dtype=torch.int32)
+
+
+@torch.library.custom_op("egorear_amd::skeleton_resize", mutates_args=(), device_types="cuda")
+def skeleton_resize_op(pose: torch.Tensor, valid: torch.Tensor, bone_length: torch.Tensor, parents: Sequence[int]) -> torch.Tensor:
+    """pose (B, J, 3) with its bones set to bone_length (J) or (B, J) along the chain: egr_skeleton_resize_f32.  Not differentiable."""
+    hip._resize_operands(pose, valid, bone_length, parents, "decode.skeleton_resize", dense=False)
+    return hip.skeleton_resize(_c(pose), _c(valid), _c(bone_length), parents)
+
+
+@skeleton_resize_op.register_fake
+def _skeleton_resize_fake(pose, valid, bone_length, parents):
+    hip._resize_operands(pose, valid, bone_length, parents, "decode.skeleton_resize", dense=False)
+    return pose.new_empty(pose.shape)
+
+
+def _nograd_setup_context_one(ctx, inputs, output):
+    _nograd_setup_context(ctx, inputs, (output,))
+
+
+skeleton_fit_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+bone_lengths_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+skeleton_resize_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context_one)
+
+
+class Skeleton3D(NamedTuple):
+    pose: torch.Tensor       # (B, J, 3) cm, device frame; 0 where not valid
+    ray_cost: torch.Tensor   # (B, J) weighted mean squared ray distance at the fitted point, cm^2 (Joints3D.cost's definition)
+    bone: torch.Tensor       # (B, J) fitted bone length to the parent, cm; 0 for the root and for a bone that is not used
+    valid: torch.Tensor      # (B, J) bool: the joint took part in the fit
+    energy0: torch.Tensor    # (B) the energy at the init
+    energy: torch.Tensor     # (B) the energy at the result, <= energy0
+    grad: torch.Tensor       # (B) largest |dE/dp| component at the result: how converged the fit is
+    steps: torch.Tensor      # (B) int32 steps kept
+
+
+class BoneStats(NamedTuple):
+    length: torch.Tensor     # (J) mean bone length over the frames where both ends are valid, cm; 0 for the root and when count is 0
+    spread: torch.Tensor     # (J) its standard deviation, cm
+    count: torch.Tensor      # (J) int32 those frames
+
+
+def _as_flags(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.uint8) if t.dtype == torch.bool else t       # (a reinterpretation, not a copy)
+
+
+def fit_skeleton(coords: torch.Tensor, conf: torch.Tensor, cameras: Union[str, Sequence], bone_length: torch.Tensor, init: torch.Tensor,
+                 init_ok: Optional[torch.Tensor] = None, parents: Optional[Sequence[int]] = None,
+                 coord_trans_mat: Optional[torch.Tensor] = None, heatmap_size: Tuple[float, float] = (64, 64), threshold: float = 0.5,
+                 bone_weight: float = 1.0, prior_weight: float = 0.0, iterations: int = 16, min_det_ratio: float = 1e-6,
+                 camera_calib_file_dir_path: Optional[str] = None) -> Skeleton3D:
+    """coords (B, V, J, 2), conf (B, V, J), `cameras`, `coord_trans_mat`, `heatmap_size`, `threshold` as for `triangulate_joints`;
+    bone_length (J) or (B, J) cm (`estimate_bone_lengths`, or the wearer's measurements; an entry <= 0 frees that bone); init (B, J, 3)
+    cm - a triangulation, a lifting head's pose, the previous frame's fit - and init_ok (B, J) bool / uint8 (None: every joint)
+    -> Skeleton3D: the joints that minimise  sum conf * dist^2(joint, its rays) + bone_weight * sum (bone - length)^2 + prior_weight *
+    sum |joint - init|^2  along the tree `parents` (None: the 16- or 15-joint table by J).  With prior_weight 0 a joint takes part
+    when its init is ok and its own rays fix it, or one ray and a bone to a parent that takes part do - so a joint that only one
+    camera sees is placed, which the triangulation cannot do; with prior_weight > 0 every joint with an init takes part.
+    `iterations` (1..256) Levenberg-Marquardt iterations on the Gauss-Newton model run, always.  Convergence is linear and depends on
+    the scene: 16 regularise a triangulation; from 3 cm off at 0.1 px of noise most scenes reach fp32 stationarity in 16 to 32 and
+    some need up to 176; at 0.3 px a few did not reach it within the 256 allowed - `grad` reports how stationary the
+    result is, and the previous frame's fit as `init` is the cheap way to be close.  One launch; nothing here is differentiable."""
+    sx, sy = _scales(heatmap_size)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, coords.device)
+    if coords.dim() != 4:
+        raise ValueError(f"egorear_amd.decode.fit_skeleton: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    table = _parents_for(parents, int(coords.shape[2]), "fit_skeleton")
+    if init_ok is None:
+        init_ok = torch.ones(coords.shape[0], coords.shape[2], dtype=torch.uint8, device=coords.device)
+    init_ok = _as_flags(init_ok)
+    table = hip._skeleton_operands(coords, conf, cams, coord_trans_mat, table, bone_length, init, init_ok, sx, sy, float(min_det_ratio),
+                                   float(bone_weight), float(prior_weight), iterations, "decode.fit_skeleton", dense=False)[3]
+    hip._on_device("decode.fit_skeleton", coords, conf, coord_trans_mat, bone_length, init, init_ok, exc=ValueError)
+    pose, ray_cost, bone, valid, energy0, energy, grad, steps = skeleton_fit_op(
+        coords, conf, cams, coord_trans_mat, table, bone_length, init, init_ok, sx, sy, float(threshold), float(min_det_ratio),
+        float(bone_weight), float(prior_weight), iterations)
+    return Skeleton3D(pose, ray_cost, bone, valid.view(torch.bool), energy0, energy, grad, steps)
+
+
+def estimate_bone_lengths(pose: torch.Tensor, valid: torch.Tensor, parents: Optional[Sequence[int]] = None) -> BoneStats:
+    """pose (B, J, 3) cm and valid (B, J) of a clip -> BoneStats(length, spread, count): every bone's mean length and standard
+    deviation over the frames in which both of its ends are valid - where `bone_length` comes from when nobody measured the wearer.
+    One launch, bit-reproducible; not differentiable."""
+    if pose.dim() != 3:
+        raise ValueError(f"egorear_amd.decode.estimate_bone_lengths: pose must be (B, J, 3), got {tuple(pose.shape)}")
+    table = _parents_for(parents, int(pose.shape[1]), "estimate_bone_lengths")
+    valid = _as_flags(valid)
+    table = hip._pose_operands(pose, valid, table, "decode.estimate_bone_lengths", dense=False)[2]
+    hip._on_device("decode.estimate_bone_lengths", pose, valid, exc=ValueError)
+    return BoneStats(*bone_lengths_op(pose, valid, table))
+
+
+def resize_skeleton(pose: torch.Tensor, valid: torch.Tensor, bone_length: torch.Tensor, parents: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """`Skeleton._skeleton_resize` (utils/skeleton.py:163-174) in cm: pose (B, J, 3), valid (B, J), bone_length (J) or (B, J) -> the
+    pose with every bone between two valid joints rescaled to its length, walking the tree from the root - each error moves everything
+    below it, and the cameras are not asked: the baseline `fit_skeleton` is compared with.  A joint that is not valid keeps its place
+    and its children start chains of their own.  One launch; not differentiable."""
+    if pose.dim() != 3:
+        raise ValueError(f"egorear_amd.decode.resize_skeleton: pose must be (B, J, 3), got {tuple(pose.shape)}")
+    table = _parents_for(parents, int(pose.shape[1]), "resize_skeleton")
+    valid = _as_flags(valid)
+    table = hip._resize_operands(pose, valid, bone_length, table, "decode.resize_skeleton", dense=False)[2]
+    hip._on_device("decode.resize_skeleton", pose, valid, bone_length, exc=ValueError)
+    return skeleton_resize_op(pose, valid, bone_length, table)
+
+
+def decode_joints_3d_skeleton(heatmaps: torch.Tensor, cameras: Union[str, Sequence], bone_length: torch.Tensor,
+                              init: Optional[torch.Tensor] = None, init_ok: Optional[torch.Tensor] = None,
+                              parents: Optional[Sequence[int]] = None, coord_trans_mat: Optional[torch.Tensor] = None, beta: float = 100.0,
+                              threshold: float = 0.5, bone_weight: float = 1.0, prior_weight: float = 0.0, iterations: int = 16,
+                              min_det_ratio: float = 1e-6, camera_calib_file_dir_path: Optional[str] = None
+                              ) -> Tuple[Skeleton3D, Joints3D, Joints2D]:
+    """heatmaps (B, V, J, H, W) -> (Skeleton3D, Joints3D, Joints2D): `decode_joints_3d` (soft-argmax at `beta`, triangulation), then
+    `fit_skeleton` on the same 2-D joints - three launches.  Without `init` the fit starts from the triangulated pose and takes its
+    `valid` as init_ok: it only regularises what the triangulation found.  With the caller's init (B, J, 3) - the lifting head's pose,
+    the previous frame's fit - and init_ok (B, J; None: every joint) it also places joints that fewer than two cameras see; a joint the
+    caller's init_ok leaves out starts from the triangulated point where that is valid (one torch.where between the launches).
+    Nothing in the fit is differentiable; the triangulated pose and cost keep their gradients."""
+    what = "decode.decode_joints_3d_skeleton"
+    # (what the fit would refuse is refused before the soft-argmax runs)
+    if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (B, V, J, H, W) with 2 to 4 views, got {tuple(heatmaps.shape)}")
+    B, J = int(heatmaps.shape[0]), int(heatmaps.shape[2])
+    parents, _ = hip._skeleton_parameters(B, J, _parents_for(parents, J, "decode_joints_3d_skeleton"), bone_length, init,
+                                          None if init_ok is None else _as_flags(init_ok), float(bone_weight), float(prior_weight),
+                                          iterations, what, dense=False)
+    hip._on_device(what, heatmaps, coord_trans_mat, bone_length, init, init_ok, exc=ValueError)
+    joints3d, joints2d = decode_joints_3d(heatmaps, cameras, coord_trans_mat, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
+    H, W = int(heatmaps.shape[-2]), int(heatmaps.shape[-1])
+    tri, tri_ok = joints3d.pose.detach(), joints3d.valid
+    if init is None:
+        start, start_ok = tri, tri_ok
+    else:
+        if init_ok is None:
+            start, start_ok = init, torch.ones_like(tri_ok)
+        else:
+            mine = init_ok.view(torch.bool) if init_ok.dtype == torch.uint8 else init_ok
+            start, start_ok = torch.where(mine.unsqueeze(-1), init, tri), mine | tri_ok
+    fit = fit_skeleton(joints2d.soft.detach(), joints2d.maxvals.detach(), cameras, bone_length, start, start_ok, parents, coord_trans_mat,
+                       (H, W), threshold, bone_weight, prior_weight, iterations, min_det_ratio, camera_calib_file_dir_path)
+    return fit, joints3d, joints2d

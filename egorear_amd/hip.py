@@ -186,7 +186,7 @@ EXPORTS = [
     "egr_jqa_query_f32", "egr_pose_query_f32", "egr_layer_set_planes", "egr_head_set_persist", "egr_heatmap_metrics_f32",
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
     "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
-    "egr_peaks_f32", "egr_consensus_f32",
+    "egr_peaks_f32", "egr_consensus_f32", "egr_skeleton_fit_f32", "egr_bone_lengths_f32", "egr_skeleton_resize_f32",
 ]
 
 
@@ -313,6 +313,10 @@ def _load() -> C.CDLL:
     lib.egr_volume_fuse_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]
     lib.egr_peaks_f32.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.egr_consensus_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, i32, f32, vp, vp, vp, vp, vp, vp, vp]
+    lib.egr_skeleton_fit_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, vp]
+    lib.egr_bone_lengths_f32.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.egr_skeleton_resize_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -1530,6 +1534,155 @@ def consensus(cand: torch.Tensor, cscore: torch.Tensor, cindex: torch.Tensor, ca
             _p(score), _p(inliers, torch.int32), _p(hyp, torch.int32), _stream(),
             nbytes=B * J * (V * (16.0 * K + 16.0 + (64.0 if ctm is not None else 0.0)) + 12.0))
     return choice, sel_coords, sel_conf, score, inliers, hyp
+
+
+SKELETON_MAX_J = 16           # joints of one tree of egr_skeleton.hip: a lane a joint, 4 bits a parent
+SKELETON_MAX_ITERATIONS = 256
+
+
+def _parents(what: str, parents, J: int):
+    """The parent table as a list of J integers (host memory: it travels to the kernel by value): parents[0] == 0 and
+    0 <= parents[j] < j."""
+    if isinstance(parents, torch.Tensor):
+        if parents.device.type != "cpu" or parents.dtype.is_floating_point or parents.dim() != 1:
+            raise ValueError(f"egorear_amd.{what}: parents must be a sequence of integers or a 1-D integer tensor in host memory")
+        parents = parents.tolist()
+    try:
+        table = [int(v) for v in parents]
+        exact = all(not isinstance(v, bool) and int(v) == v for v in parents)
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.{what}: parents must be a sequence of integers, got {parents!r}") from None
+    if not 1 <= J <= SKELETON_MAX_J:
+        raise ValueError(f"egorear_amd.{what}: 1 to {SKELETON_MAX_J} joints are supported, got {J}")
+    if not exact or len(table) != J:
+        raise ValueError(f"egorear_amd.{what}: parents must be {J} integers, got {parents!r}")
+    if table[0] != 0 or any(not 0 <= table[j] < j for j in range(1, J)):
+        raise ValueError(f"egorear_amd.{what}: parents[0] must be 0 and 0 <= parents[j] < j (a parent comes before its children), got {table}")
+    return table
+
+
+def _host_table(table):
+    return (C.c_int32 * len(table))(*table)
+
+
+def _bone_length(what: str, bone_length, B: int, J: int) -> int:
+    """1 when the lengths are per frame (B, J), 0 for one (J) table."""
+    if tuple(bone_length.shape) not in ((J,), (B, J)):
+        raise ValueError(f"egorear_amd.{what}: bone_length must be {(J,)} or {(B, J)}, got {tuple(bone_length.shape)}")
+    return int(bone_length.dim() == 2)
+
+
+def _flags(what: str, t, shape, name: str):
+    if tuple(t.shape) != shape or t.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"egorear_amd.{what}: {name} must be a uint8 or bool {shape}, got {t.dtype} {tuple(t.shape)}")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _fit_parameters(what: str, bone_weight, prior_weight, iterations):
+    _non_negative(what, "bone_weight", bone_weight)
+    _non_negative(what, "prior_weight", prior_weight)
+    if not _int_in(iterations, 1, SKELETON_MAX_ITERATIONS):
+        raise ValueError(f"egorear_amd.{what}: iterations must be an integer in 1..{SKELETON_MAX_ITERATIONS}, got {iterations!r}")
+
+
+def _skeleton_parameters(B: int, J: int, parents, bone_length, init, init_ok, bone_weight, prior_weight, iterations, what: str,
+                         dense: bool = True):
+    """What a skeleton fit takes besides the triangulation's operands -> (the host parent table, per-frame lengths?).  `init` and
+    `init_ok` may be None where a chain makes them itself (decode.decode_joints_3d_skeleton validates before its first launch)."""
+    table = _parents(what, parents, J)
+    per_frame = _bone_length(what, bone_length, B, J)
+    if init is not None and tuple(init.shape) != (B, J, 3):
+        raise ValueError(f"egorear_amd.{what}: init must be {(B, J, 3)}, got {tuple(init.shape)}")
+    if init_ok is not None:
+        _flags(what, init_ok, (B, J), "init_ok")
+    _float32(what, (bone_length, "bone_length"), (init, "init"))
+    _fit_parameters(what, bone_weight, prior_weight, iterations)
+    _contiguous(what, dense, (bone_length, "bone_length"), (init, "init"), (init_ok, "init_ok"))
+    return table, per_frame
+
+
+def _skeleton_operands(coords, conf, cams, ctm, parents, bone_length, init, init_ok, sx, sy, min_det_ratio, bone_weight, prior_weight,
+                       iterations, what: str, dense: bool = True):
+    """(B, V, J, the host parent table, per-frame lengths?) of a skeleton fit; every shape / dtype / parameter error as ValueError."""
+    B, V, J = _tri_operands(coords, conf, cams, ctm, sx, sy, min_det_ratio, what, dense=dense)
+    if init is None or init_ok is None:
+        raise ValueError(f"egorear_amd.{what}: init and init_ok are required")
+    table, per_frame = _skeleton_parameters(B, J, parents, bone_length, init, init_ok, bone_weight, prior_weight, iterations, what, dense)
+    return B, V, J, table, per_frame
+
+
+def skeleton_fit(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], parents, bone_length: torch.Tensor,
+                 init: torch.Tensor, init_ok: torch.Tensor, sx: float = 1.0, sy: float = 1.0, threshold: float = 0.5,
+                 min_det_ratio: float = 1e-6, bone_weight: float = 1.0, prior_weight: float = 0.0, iterations: int = 16):
+    """coords (B,V,J,2), conf (B,V,J), cams (V,30), ctm (B,V,4,4) | None as for triangulate; parents: J host integers; bone_length (J) |
+    (B,J) cm; init (B,J,3) cm, init_ok (B,J) u8 -> pose (B,J,3), ray_cost (B,J), bone (B,J), valid (B,J) u8, energy0 (B), energy (B),
+    grad (B), steps (B) i32: egr_skeleton_fit_f32, the joints that minimise the rays' distances plus bone_weight * the squared
+    bone-length errors plus prior_weight * the squared distances from init (include/egorear_hip.h states the energy and the solver)."""
+    B, V, J, table, per_frame = _skeleton_operands(coords, conf, cams, ctm, parents, bone_length, init, init_ok, sx, sy, min_det_ratio,
+                                                   bone_weight, prior_weight, iterations, "skeleton_fit")
+    _on_device("skeleton_fit", coords, conf, cams, ctm, bone_length, init, init_ok)
+    init_ok = _flags("skeleton_fit", init_ok, (B, J), "init_ok")
+    dev = coords.device
+    pose = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+    ray_cost, bone = (torch.empty((B, J), device=dev, dtype=torch.float32) for _ in range(2))
+    valid = torch.empty((B, J), device=dev, dtype=torch.uint8)
+    energy0, energy, grad = (torch.empty((B,), device=dev, dtype=torch.float32) for _ in range(3))
+    steps = torch.empty((B,), device=dev, dtype=torch.int32)
+    _launch("egr_skeleton_fit_f32", lib.egr_skeleton_fit_f32, _p(coords), _p(conf), _p(cams), _p(ctm), _host_table(table), _p(bone_length),
+            per_frame,
+            _p(init), _p(init_ok, torch.uint8), B, V, J, float(sx), float(sy), float(threshold), float(min_det_ratio), float(bone_weight),
+            float(prior_weight), int(iterations), _p(pose), _p(ray_cost), _p(bone), _p(valid, torch.uint8), _p(energy0), _p(energy), _p(grad),
+            _p(steps, torch.int32), _stream(), nbytes=B * (J * (V * 12.0 + 38.0) + (V * 64.0 if ctm is not None else 0.0) + 16.0))
+    return pose, ray_cost, bone, valid, energy0, energy, grad, steps
+
+
+def _pose_operands(pose, valid, parents, what: str, dense: bool = True):
+    """(B, J, the host parent table) of the launches on fitted poses; every shape / dtype error as ValueError."""
+    if pose.dim() != 3 or pose.shape[-1] != 3:
+        raise ValueError(f"egorear_amd.{what}: pose must be (B, J, 3), got {tuple(pose.shape)}")
+    B, J = int(pose.shape[0]), int(pose.shape[1])
+    if B < 1:
+        raise ValueError(f"egorear_amd.{what}: empty pose {tuple(pose.shape)}")
+    table = _parents(what, parents, J)
+    _flags(what, valid, (B, J), "valid")
+    _float32(what, (pose, "pose"))
+    _contiguous(what, dense, (pose, "pose"), (valid, "valid"))
+    return B, J, table
+
+
+def bone_lengths(pose: torch.Tensor, valid: torch.Tensor, parents):
+    """pose (B,J,3), valid (B,J) u8, parents: J host integers -> length (J), spread (J), count (J) i32: egr_bone_lengths_f32, mean and
+    standard deviation of every bone over the frames of the clip in which both of its ends are valid."""
+    B, J, table = _pose_operands(pose, valid, parents, "bone_lengths")
+    _on_device("bone_lengths", pose, valid)
+    valid = _flags("bone_lengths", valid, (B, J), "valid")
+    dev = pose.device
+    length, spread = (torch.empty((J,), device=dev, dtype=torch.float32) for _ in range(2))
+    count = torch.empty((J,), device=dev, dtype=torch.int32)
+    _launch("egr_bone_lengths_f32", lib.egr_bone_lengths_f32, _p(pose), _p(valid, torch.uint8), _host_table(table), B, J, _p(length), _p(spread),
+            _p(count, torch.int32), _stream(), nbytes=B * J * 26.0 + J * 12.0)
+    return length, spread, count
+
+
+def _resize_operands(pose, valid, bone_length, parents, what: str, dense: bool = True):
+    B, J, table = _pose_operands(pose, valid, parents, what, dense)
+    per_frame = _bone_length(what, bone_length, B, J)
+    _float32(what, (bone_length, "bone_length"))
+    _contiguous(what, dense, (bone_length, "bone_length"))
+    return B, J, table, per_frame
+
+
+def skeleton_resize(pose: torch.Tensor, valid: torch.Tensor, bone_length: torch.Tensor, parents) -> torch.Tensor:
+    """pose (B,J,3), valid (B,J) u8, bone_length (J) | (B,J) cm, parents: J host integers -> the pose with every bone between two valid
+    joints set to its length along the kinematic chain: egr_skeleton_resize_f32, the reference's Skeleton._skeleton_resize in cm."""
+    B, J, table, per_frame = _resize_operands(pose, valid, bone_length, parents, "skeleton_resize")
+    _on_device("skeleton_resize", pose, valid, bone_length)
+    valid = _flags("skeleton_resize", valid, (B, J), "valid")
+    out = torch.empty_like(pose)
+    _launch("egr_skeleton_resize_f32", lib.egr_skeleton_resize_f32, _p(pose), _p(valid, torch.uint8), _host_table(table), _p(bone_length), per_frame,
+            B, J,
+            _p(out), _stream(), nbytes=B * J * 29.0)
+    return out
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -556,6 +556,54 @@ int egr_consensus_f32(const float* cand, const float* cscore, const int32_t* cin
                       float* sel_conf /* B x V x J */, float* score /* B x J */, int32_t* inliers /* B x J */, int32_t* hyp /* B x J */,
                       void* stream);
 
+/* Bone-length-constrained skeleton fit over the fisheye rays.  Per frame, over the active joints p_j (cm, device frame)
+ * of a tree of J <= 16 joints, minimise
+ *   E(p) = sum_j sum_v w_vj dist^2(p_j, ray_vj) + lambda sum_{j > 0, bone j used} (|p_j - p_parent(j)| - L_j)^2 + rho sum_j |p_j - init_j|^2.
+ *   coords, conf, cams, ctm, sx, sy, threshold, min_det_ratio as for egr_triangulate_f32: the same rays, the same views used or
+ *   excluded, w = conf.  parents: J int32 in HOST memory, parents[0] == 0 and 0 <= parents[j] < j (checked here; it travels to the
+ *   kernel by value).  bone_length (J), or (B, J) with bone_length_per_frame != 0, cm: entry 0 is ignored, an entry <= 0 or not finite
+ *   leaves that bone unconstrained.  init (B, J, 3) cm and init_ok (B, J): an init with a non-finite component counts as not ok.
+ *   Active joints, decided once per frame in index order: with rho > 0 a joint is active iff its init is ok; with rho == 0 iff its
+ *   init is ok and either its own rays fix it (egr_triangulate_f32's ok: two used views or more and the normal equations factor) or it
+ *   has at least one used view and a constrained bone to an active parent.  A joint is never anchored from a child: a joint whose
+ *   only support is a bone to a child below it is not active at rho == 0.  A bone is used iff both ends are active and its length is
+ *   constrained; a bone shorter than 1e-9 cm contributes its constant residual and no gradient.
+ *   Solver: Levenberg-Marquardt on the Gauss-Newton model (the data and prior terms are exact quadratics, a used bone contributes
+ *   lambda u u^T blocks, u = d / |d|): every iteration solves (H + mu diag H) delta = -g at the current p - eliminated along the tree
+ *   from the deepest joints to the roots in 3 x 3 LDL^T steps, a parent folding its children in index order, then back-substituted -
+ *   and keeps p + delta iff every block factored and E(p + delta) <= E(p) - the change evaluated as a difference (exactly for the
+ *   quadratic terms, through len' - len for a bone), so that steps below the rounding of E are still decided.  mu starts at 1e-3; a kept step multiplies it by 0.1 (not
+ *   below 1e-12), a refused one by 10 (not above 1e12).  `iterations` (1..256) such iterations run, always.  One block that does not
+ *   factor refuses the step for the whole frame.  Convergence is linear: where bones end under tension or compression and the rays
+ *   are soft along the viewing direction, fp32 stationarity can take more than the 256 iterations (`grad` says how far it got).
+ * pose (B, J, 3): 0 where not valid; ray_cost (B, J): sum_v w dist^2 / sum_v w at the fitted point (egr_triangulate_f32's cost), 0
+ * without a used view; bone (B, J): the fitted length, 0 for the root and for a bone that is not used; valid (B, J): 1 when active;
+ * energy0 (B), energy (B): E at the init and at the result, each the three sums evaluated there (no kept step raises E, so energy
+ * <= energy0 up to the rounding of the two sums: an fp32 ulp of energy0 at most, where no step lowered it); grad (B): the largest
+ * |dE/dp| component over the active joints at the result; steps (B): the kept steps.  A frame without an active joint gives zeros.
+ * One wave per frame: lane v*16 + j builds the ray of view v of joint j once, lane j owns joint j's block, parents and children
+ * exchange by cross-lane reads; fp64 arithmetic on fp32 operands, no atomics, no LDS: the same bits every run, alone or in a batch.
+ * EGR_EINVAL: the shapes egr_triangulate_f32 refuses, J > 16, a bad parent table, lambda or rho negative or not finite, iterations
+ * outside 1..256. */
+int egr_skeleton_fit_f32(const float* coords, const float* conf, const float* cams, const float* ctm /* nullable */,
+                         const int32_t* parents /* J, host */, const float* bone_length, int32_t bone_length_per_frame, const float* init,
+                         const uint8_t* init_ok, int32_t B, int32_t V, int32_t J, float sx, float sy, float threshold, float min_det_ratio,
+                         float lambda, float rho, int32_t iterations, float* pose /* B x J x 3 */, float* ray_cost /* B x J */,
+                         float* bone /* B x J */, uint8_t* valid /* B x J */, float* energy0 /* B */, float* energy /* B */,
+                         float* grad /* B */, int32_t* steps /* B */, void* stream);
+/* Bone statistics of a clip: pose (B, J, 3), valid (B, J), parents as above (host) -> length (J), spread (J) - mean and (population)
+ * standard deviation of |p_j - p_parent(j)| over the frames in which both ends are valid - and count (J), those frames.  Entry 0 and a
+ * bone with count 0 give 0.  One thread per bone, fp64 sums in frame order (the mean, then the deviations): bit-reproducible. */
+int egr_bone_lengths_f32(const float* pose, const uint8_t* valid, const int32_t* parents /* J, host */, int32_t B, int32_t J, float* length,
+                         float* spread, int32_t* count, void* stream);
+/* Skeleton._skeleton_resize (pose_estimation/utils/skeleton.py:163-174) in cm (the reference works in mm and divides by 1000; nothing
+ * is divided here): the tree is walked in index order, out_j = out_parent(j) + (p_j - p_parent(j)) * L_j / |p_j - p_parent(j)|, the
+ * direction taken from the input pose.  A joint with valid 0 keeps its place, and so does a joint whose parent is not valid - it
+ * starts a chain of its own.  A bone whose length is <= 0 or not finite, or shorter than 1e-9 cm in the input, keeps its vector.
+ * bone_length (J), or (B, J) with bone_length_per_frame != 0.  One thread per frame; out must not be pose. */
+int egr_skeleton_resize_f32(const float* pose, const uint8_t* valid, const int32_t* parents /* J, host */, const float* bone_length,
+                            int32_t bone_length_per_frame, int32_t B, int32_t J, float* out /* B x J x 3 */, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
