@@ -1,12 +1,13 @@
 """Float64 statements of the multi-peak decoder (egr_peaks_f32) and of the consensus over its candidates (egr_consensus_f32), DESIGN.md 5p,
 written in elementwise torch operations, plus the distractor scene the robust chain is judged on.  Shared by test_robust_decode_host.py,
 test_gpu_peaks.py, test_gpu_consensus.py and tools/robust_accuracy.py; every function computes in the dtype of its first operand, so
-the same code gives the float64 statement and torch's fp32 evaluation of it (the yardstick of test_gpu_triangulate.py)."""
+the same code gives the float64 statement and torch's fp32 evaluation of it (the yardstick of fisheye_statement.py).  The camera math -
+the triangulation of a hypothesis and the Horner projection of its point - is fisheye_statement's."""
 import torch
 
-import test_gpu_triangulate as TT
+import fisheye_statement as FS
 
-HM = 64
+HM = FS.HM
 NEG = float("-inf")
 
 
@@ -61,27 +62,11 @@ def view_pairs(V):
     return [(a, b) for a in range(V) for b in range(a + 1, V)]
 
 
-def project_to(pts, rec, ctm, sx, sy):
-    """pts (B, J, 3) cm in their own dtype -> the unclamped projections (B, V, J, 2) in coords units (image pixels / (sx W_img))."""
-    dt = pts.dtype
-    B, J, _ = pts.shape
-    V = rec.shape[0]
-    c = rec.to(dt)
-    R, t = TT.extrinsics(rec, ctm, B, V, dt)
-    p = [pts[..., k].unsqueeze(1) for k in range(3)]
-    q = [sum(R[r][k] * p[k] for k in range(3)) + t[r] for r in range(3)]
-    norm = torch.sqrt(q[0] * q[0] + q[1] * q[1])
-    rho = TT._poly(c[:, 5:17], torch.atan2(-q[2], norm), 12)
-    u = (q[0] / norm * rho + c[:, 1].view(1, V, 1)) / (sx * c[:, 3].view(1, V, 1))
-    v = (q[1] / norm * rho + c[:, 2].view(1, V, 1)) / (sy * c[:, 4].view(1, V, 1))
-    return torch.stack((u, v), -1)
-
-
 def candidates_exist(cand, cscore, cindex):
     return (cindex >= 0) & torch.isfinite(cscore) & (cscore > 0) & torch.isfinite(cand).all(-1)
 
 
-def consensus_statement(cand, cscore, cindex, rec, ctm, sx, sy, tau, min_views, min_det_ratio=TT.MIN_DET):
+def consensus_statement(cand, cscore, cindex, rec, ctm, sx, sy, tau, min_views, min_det_ratio=FS.MIN_DET):
     """cand (B, V, J, K, 2), cscore (B, V, J, K) in their own dtype, cindex (B, V, J, K) -> dict: choice (B, V, J), sel_coords, sel_conf,
     score (B, J), inliers, hyp, and per hypothesis h: all_score (B, J, NH), all_ok (B, J, NH) = qualifies, all_choice (B, J, NH, V)."""
     dt = cand.dtype
@@ -99,8 +84,8 @@ def consensus_statement(cand, cscore, cindex, rec, ctm, sx, sy, tau, min_views, 
             for kb in range(K):
                 c2 = torch.stack((xy[:, a, :, ka], xy[:, b, :, kb]), 1)
                 w2 = torch.stack((w[:, a, :, ka], w[:, b, :, kb]), 1)
-                p, _, _, ok = TT.statement(c2, w2, rec2, ctm2, sx, sy, thr=0.0, min_det_ratio=min_det_ratio)
-                proj = project_to(p, rec, ctm_d, sx, sy)                                   # (B, V, J, 2)
+                p, _, _, ok = FS.statement(c2, w2, rec2, ctm2, sx, sy, thr=0.0, min_det_ratio=min_det_ratio)
+                proj = FS.project(p, rec, ctm_d, sx, sy)                                    # (B, V, J, 2)
                 e2 = ((proj.unsqueeze(3) - xy) ** 2).sum(-1)                               # (B, V, J, K)
                 keep = 1.0 - e2 / (tau * tau)
                 term = torch.where(exists & (keep > 0), w * keep, zero)                    # (a NaN fails the comparison)
@@ -152,18 +137,17 @@ def decided(ref, rel=1e-6):
 # --------------------------------------------------------------------------- the distractor scene
 
 def distractor_scene(B, views=(0, 1, 2, 3), seed=77, J=15, distract=1, height=1.2):
-    """Sigma-1 bumps on 64 x 64 maps at the syn rig's projections of random points (test_gpu_triangulate.py's round-trip scene: seed 77,
+    """Sigma-1 bumps on 64 x 64 maps at the syn rig's projections of random points (test_gpu_triangulate.py's bump_maps scene: seed 77,
     15 joints a frame), plus, in `distract` different views per joint, one extra bump of `height` at a random spot more than 10 px from
     the true one.  -> dict: cams, rec, pts (B, J, 3) float64, hm (B, V, J, 64, 64) float32, centre (B, V, J, 2), which (B, J, distract)."""
     g = torch.Generator().manual_seed(seed)
-    cams = [TT.rig()[v] for v in views]
-    rec = TT.records(cams)
+    cams = [FS.rig()[v] for v in views]
+    rec = FS.records(cams)
     V = len(views)
-    pts = TT.random_points(B, J, g)
-    centre = TT.project(pts, rec, None) * HM
+    pts = FS.random_points(B, J, g)
+    centre = FS.project(pts, rec, None) * HM
     assert bool(((centre > 0) & (centre < HM - 1)).all()), "a projection left the image"
-    xs, ys = torch.arange(HM, dtype=torch.float64).view(1, 1, 1, 1, HM), torch.arange(HM, dtype=torch.float64).view(1, 1, 1, HM, 1)
-    hm = torch.exp(-((xs - centre[..., 0, None, None]) ** 2 + (ys - centre[..., 1, None, None]) ** 2) / 2.0)
+    hm = FS.bumps(pts, rec, None, HM, HM)
     g2 = torch.Generator().manual_seed(seed + 1)
     which = torch.stack([torch.randperm(V, generator=g2)[:distract] for _ in range(B * J)]).view(B, J, distract)
     for b in range(B):
@@ -173,7 +157,7 @@ def distractor_scene(B, views=(0, 1, 2, 3), seed=77, J=15, distract=1, height=1.
                     spot = torch.rand(2, generator=g2, dtype=torch.float64) * (HM - 5) + 2
                     if float((spot - centre[b, v, j]).norm()) > 10.0:
                         break
-                hm[b, v, j] += height * torch.exp(-((xs[0, 0, 0] - spot[0]) ** 2 + (ys[0, 0, 0] - spot[1]) ** 2) / 2.0)
+                hm[b, v, j] += height * FS.render(spot[0], spot[1], HM, HM)
     return {"cams": cams, "rec": rec, "pts": pts, "hm": hm.float().contiguous(), "centre": centre, "which": which}
 
 
@@ -184,13 +168,13 @@ def robust_chain(hm, rec, ctm=None, K=3, rn=1, r=2, beta=100.0, thr=0.5, tau=2.0
     coords, score, index, count = peaks_statement(hm.reshape(-1, H, W), K, rn, r, beta, thr)
     cand, cscore, cindex = coords.view(B, V, J, K, 2), score.view(B, V, J, K), index.view(B, V, J, K)
     con = consensus_statement(cand, cscore, cindex, rec, ctm, 1.0 / W, 1.0 / H, tau, min_views)
-    pose, _, _, ok = TT.statement(con["sel_coords"], con["sel_conf"], rec, ctm, 1.0 / W, 1.0 / H, thr)
+    pose, _, _, ok = FS.statement(con["sel_coords"], con["sel_conf"], rec, ctm, 1.0 / W, 1.0 / H, thr)
     return pose, ok, con, (cand, cscore, cindex, count.view(B, V, J))
 
 
 def top1_chain(hm, rec, ctm=None, beta=100.0, thr=0.5):
     """What decode_joints_3d does, as statements: the whole-map soft-argmax, then the triangulation of every view."""
     H, W = hm.shape[-2:]
-    c, m = TT._soft_argmax64(hm, beta)
-    pose, _, _, ok = TT.statement(c, m, rec, ctm, 1.0 / W, 1.0 / H, thr)
+    c, m = FS.soft_argmax_statement(hm, beta)
+    pose, _, _, ok = FS.statement(c, m, rec, ctm, 1.0 / W, 1.0 / H, thr)
     return pose, ok

@@ -1,7 +1,7 @@
 """Statements of the bone-length-constrained skeleton fit (egr_skeleton_fit_f32) and of the two small launches that belong with it
 (egr_bone_lengths_f32, egr_skeleton_resize_f32), DESIGN.md 5q, in torch, so that they run in float64 and in float32:
 
-  energy          nothing but the three sums of the energy, on the rays of test_gpu_triangulate's statement;
+  energy          nothing but the three sums of the energy, on the rays of fisheye_statement.py (the triangulation's);
   fit_statement   the kernel's algorithm - Levenberg-Marquardt on the Gauss-Newton model with the header's damping schedule - with a
                   dense Cholesky solve in place of the elimination along the tree;
   newton_referee  a different algorithm: full Newton on the exact autograd Hessian with a backtracking line search, to |grad| < 1e-10;
@@ -12,9 +12,9 @@ import math
 
 import torch
 
-import test_gpu_triangulate as TT
+import fisheye_statement as FS
 
-HM = TT.HM
+HM = FS.HM
 MU0, MU_DOWN, MU_UP, MU_MIN, MU_MAX = 1e-3, 0.1, 10.0, 1e-12, 1e12     # the damping schedule of include/egorear_hip.h
 MIN_BONE = 1e-9
 PARENTS_16 = (0, 0, 1, 1, 2, 3, 4, 5, 2, 3, 8, 9, 10, 11, 12, 13)        # Skeleton.kinematic_parents of the reference
@@ -25,42 +25,17 @@ def parents_15():
     return tuple(max(p - 1, 0) for p in PARENTS_16[1:])
 
 
-# --------------------------------------------------------------------------- the rays (the first half of TT.statement)
-
-def rays(coords, conf, rec, ctm, sx, sy, thr, newton=6):
-    """w (B, V, J), d[3], R[3][3], t[3] (broadcastable to (B, V, J)): TT.statement's rays, line by line."""
-    dt = coords.dtype
-    B, V, J = conf.shape
-    c = rec.to(dt)
-    x, y = coords[..., 0], coords[..., 1]
-    use = (conf >= thr) & (conf > 0) & torch.isfinite(conf) & torch.isfinite(x) & torch.isfinite(y)
-    zero = torch.zeros_like(conf)
-    w, x, y = torch.where(use, conf, zero), torch.where(use, x, zero + 0.5 / sx), torch.where(use, y, zero + 0.5 / sy)
-    col = lambda i: c[:, i].view(1, V, 1)
-    dx, dy = x * sx * col(3) - col(1), y * sy * col(4) - col(2)
-    rho = torch.sqrt(dx * dx + dy * dy)
-    axis = ~(rho >= 1e-4)
-    rs = torch.where(axis, torch.ones_like(rho), rho)
-    ux, uy = torch.where(axis, zero, dx / rs), torch.where(axis, zero, dy / rs)
-    theta = torch.atan(TT._poly(c[:, 18:26], rs, 8) / rs)
-    for _ in range(newton):
-        theta = theta - (TT._poly(c[:, 5:17], theta, 12) - rs) / TT._dpoly(c[:, 5:17], theta, 12)
-    st, ct = torch.where(axis, -torch.ones_like(rho), torch.sin(theta)), torch.where(axis, zero, torch.cos(theta))
-    R, t = TT.extrinsics(rec, ctm, B, V, dt)
-    return w, [ux * ct, uy * ct, -st], R, t
-
-
 class Problem:
     """One launch's operands, the rays made of them, and what is decided once per frame: which joints and bones take part."""
 
-    def __init__(self, coords, conf, rec, ctm, parents, bone_length, init, init_ok, lam, rho, sx=1.0 / HM, sy=1.0 / HM, thr=TT.THR,
-                 min_det_ratio=TT.MIN_DET):
+    def __init__(self, coords, conf, rec, ctm, parents, bone_length, init, init_ok, lam, rho, sx=1.0 / HM, sy=1.0 / HM, thr=FS.THR,
+                 min_det_ratio=FS.MIN_DET):
         dt = coords.dtype
         B, V, J = conf.shape
         self.B, self.V, self.J, self.dt, self.lam, self.rho = B, V, J, dt, float(lam), float(rho)
         self.parents = torch.tensor(list(parents), dtype=torch.int64)
-        self.w, self.d, self.R, self.t = rays(coords, conf, rec, ctm, sx, sy, thr)
-        tri_ok = TT.statement(coords, conf, rec, ctm, sx, sy, thr, min_det_ratio)[3]
+        _, self.w, self.d, self.R, self.t = FS.rays(coords, conf, rec, ctm, sx, sy, thr)
+        tri_ok = FS.statement(coords, conf, rec, ctm, sx, sy, thr, min_det_ratio)[3]
         used = (self.w > 0).sum(1)
         L = bone_length.to(dt).expand(B, J) if bone_length.dim() == 1 else bone_length.to(dt)
         constrained = (L > 0) & torch.isfinite(L)
@@ -77,24 +52,12 @@ class Problem:
         self.L = torch.where(constrained, L, torch.zeros_like(L))
         self.init = torch.where(fine.unsqueeze(-1), init, torch.zeros_like(init))
         self.wsum = self.w.sum(1)
-        # the normal equations of every joint's rays: A p = b
-        d, R, t, w = self.d, self.R, self.t, self.w
-        e = [sum(R[r][k] * d[r] for r in range(3)) for k in range(3)]
-        rt = [sum(R[r][k] * t[r] for r in range(3)) for k in range(3)]
-        d_t = sum(d[r] * t[r] for r in range(3))
-        self.A = torch.stack([torch.stack([(w * (sum(R[r][k] * R[r][l] for r in range(3)) - e[k] * e[l])).sum(1) for l in range(3)], -1)
-                              for k in range(3)], -2)                                   # (B, J, 3, 3)
-        self.b = torch.stack([-(w * (rt[k] - e[k] * d_t)).sum(1) for k in range(3)], -1)     # (B, J, 3)
+        A, b = FS.normal_equations(self.w, self.d, self.R, self.t)      # of every joint's rays: A p = b, (B, J, 3, 3) and (B, J, 3)
+        self.A = torch.stack([torch.stack([A[min(k, l), max(k, l)] for l in range(3)], -1) for k in range(3)], -2)
+        self.b = torch.stack(b, -1)
 
     def start(self):
         return torch.where(self.active.unsqueeze(-1), self.init, torch.zeros_like(self.init))
-
-
-def ray_dist2(pr, p):
-    """Squared distance of p (B, J, 3) from every view's ray, (B, V, J)."""
-    q = [sum(pr.R[r][k] * p[..., k].unsqueeze(1) for k in range(3)) + pr.t[r] for r in range(3)]
-    dq = sum(pr.d[r] * q[r] for r in range(3))
-    return sum((q[r] - pr.d[r] * dq) ** 2 for r in range(3))
 
 
 def bone_vectors(pr, p):
@@ -109,7 +72,7 @@ def bone_vectors(pr, p):
 def energy(pr, p):
     """E (B) = sum_j sum_v w dist^2 + lambda sum_bones (len - L)^2 + rho sum_j |p - init|^2 over the active joints and used bones; and
     the joints' data sums (B, J)."""
-    data = (pr.w * ray_dist2(pr, p)).sum(1)
+    data = (pr.w * FS.ray_dist2(pr.d, pr.R, pr.t, lambda k: p[..., k])).sum(1)
     prior = pr.rho * ((p - pr.init) ** 2).sum(-1)
     _, length = bone_vectors(pr, p)
     zero = torch.zeros_like(data)
@@ -309,12 +272,12 @@ def default_parents(J, chain=False):
 
 
 def random_skeleton(B, J, parents, g):
-    """Poses (B, J, 3) float64 of a skeleton whose bones (J, the same in every frame) are 10 to 35 cm, inside the box of TT.random_points."""
+    """Poses (B, J, 3) float64 of a skeleton whose bones (J, the same in every frame) are 10 to 35 cm, inside the box of FS.random_points."""
     lengths = torch.rand(J, generator=g, dtype=torch.float64) * 25 + 10
     lengths[0] = 0.0
     lo, hi = torch.tensor([-60.0, -40.0, 15.0], dtype=torch.float64), torch.tensor([60.0, 80.0, 150.0], dtype=torch.float64)
     pts = torch.zeros(B, J, 3, dtype=torch.float64)
-    pts[:, 0] = TT.random_points(B, 1, g)[:, 0] * 0.5 + torch.tensor([0.0, 10.0, 40.0], dtype=torch.float64)
+    pts[:, 0] = FS.random_points(B, 1, g)[:, 0] * 0.5 + torch.tensor([0.0, 10.0, 40.0], dtype=torch.float64)
     for j in range(1, J):
         u = torch.randn(B, 3, generator=g, dtype=torch.float64)
         u = u / u.norm(dim=-1, keepdim=True)
@@ -330,11 +293,11 @@ def scene(B, V, J, rw, chain=False, noise=0.1, off=3.0, seed=None):
     the tension is what the noise leaves at the optimum, and along the rays the data term is soft - DESIGN.md 5q has the table.)"""
     g = torch.Generator().manual_seed(1000 * B + 100 * V + J if seed is None else seed)
     parents = default_parents(J, chain)
-    cams = TT.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
-    rec = TT.records(cams)
-    ctm = TT.random_ctm(B, V, cams, g) if rw else None
+    cams = FS.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
+    rec = FS.records(cams)
+    ctm = FS.random_ctm(B, V, cams, g) if rw else None
     pts, lengths = random_skeleton(B, J, parents, g)
-    coords = (TT.project(pts, rec, ctm) * HM + noise * torch.randn(B, V, J, 2, generator=g, dtype=torch.float64)).float()
+    coords = (FS.project(pts, rec, ctm) * HM + noise * torch.randn(B, V, J, 2, generator=g, dtype=torch.float64)).float()
     conf = (torch.rand(B, V, J, generator=g) * 0.4 + 0.6).float()
     u = torch.randn(B, J, 3, generator=g, dtype=torch.float64)
     init = (pts + off * u / u.norm(dim=-1, keepdim=True)).float()
@@ -355,10 +318,6 @@ def keep_views(sc, joint, views, frame=None):
     for b in frames:
         conf[b, views:, joint] = 0.3
     return conf
-
-
-def ulp32(m):
-    return TT.ulp32(m)
 
 
 CASES = ("full", "one_view", "unseen_prior", "unseen", "no_init", "nonfinite", "free_bones")
@@ -405,12 +364,12 @@ def problem(sc, ops, lam, dt):
                    ops["init_ok"], lam, ops["rho"])
 
 
-def stationarity(pr, pose, margin=TT.MARGIN):
+def stationarity(pr, pose, margin=FS.MARGIN):
     """-> (the largest |g_i| / allowed_i over the active components, g (B, 3J), the active components (B, 3J), allowed (B, 3J)) at
     `pose`, with g and the exact H of `energy` in float64 and allowed_i = margin * sum_k |H_ik| * ulp32(max |pose|): rounding the
     minimiser to fp32 costs up to 1 / (2 margin) of that."""
     g, H = grad_hess(pr, pose.double())
-    allowed = margin * H.abs().sum(-1) * ulp32(float(pose.abs().max()))
+    allowed = margin * H.abs().sum(-1) * FS.ulp32(float(pose.abs().max()))
     m = pr.active.unsqueeze(-1).expand(pr.B, pr.J, 3).reshape(pr.B, 3 * pr.J)
     if not bool(m.any()):
         return 0.0, g, m, allowed

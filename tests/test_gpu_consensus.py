@@ -2,12 +2,12 @@
 tests/robust_statement.py, and the robust chain end to end.  The selection is discrete: `choice`, `inliers` and `hyp` must equal the
 statement's for every pair that is decided - the statement's winning score leads the best hypothesis with a different choice by more
 than 1e-6, relative - and at most 5 % of a case's pairs may be undecided, which the float64 statement alone is held to first.
-`sel_coords` / `sel_conf` are copies: bit-equal to the gathered candidates.  `score` meets the yardstick of test_gpu_triangulate.py."""
+`sel_coords` / `sel_conf` are copies: bit-equal to the gathered candidates.  `score` meets the yardstick of fisheye_statement.py."""
 import pytest
 import torch
 
+import fisheye_statement as FS
 import robust_statement as RS
-import test_gpu_triangulate as TT
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -57,11 +57,11 @@ def shape_data(shape):
         return _CACHE[shape]
     B, V, J, K, rw = shape
     g = torch.Generator().manual_seed(1000 * B + 100 * V + 10 * J + K)
-    cams = TT.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
-    rec = TT.records(cams)
-    ctm = TT.random_ctm(B, V, cams, g) if rw else None
-    pts = TT.random_points(B, J, g)
-    true = (TT.project(pts, rec, ctm) * HM).float()
+    cams = FS.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
+    rec = FS.records(cams)
+    ctm = FS.random_ctm(B, V, cams, g) if rw else None
+    pts = FS.random_points(B, J, g)
+    true = (FS.project(pts, rec, ctm) * HM).float()
     cases = {}
     for case in CASES:
         cand, cscore, cindex, mv = make_case(case, shape, g, true)
@@ -75,7 +75,7 @@ def shape_data(shape):
 def launch(d, cand, cscore, cindex, mv):
     from egorear_amd import hip
     ctm = None if d["ctm"] is None else d["ctm"].to(DEV)
-    return hip.consensus(cand.to(DEV), cscore.to(DEV), cindex.to(DEV), d["rec"].to(DEV), ctm, 1.0 / HM, 1.0 / HM, TAU, mv, TT.MIN_DET)
+    return hip.consensus(cand.to(DEV), cscore.to(DEV), cindex.to(DEV), d["rec"].to(DEV), ctm, 1.0 / HM, 1.0 / HM, TAU, mv, FS.MIN_DET)
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -105,7 +105,7 @@ def test_consensus_against_the_float64_statement(shape):
         own = f32["all_score"].gather(2, f64["hyp"].long().clamp(min=0).unsqueeze(-1)).squeeze(-1)
         keep = sure & found
         if bool(keep.any()):
-            err, allowed = TT.yardstick("score", score[keep], own[keep], f64["score"][keep])
+            err, allowed = FS.yardstick("score", score[keep], own[keep], f64["score"][keep])
             if not err <= allowed:
                 bad.append((shape, case, err, allowed))
         # what the cases are for
@@ -140,7 +140,7 @@ def test_two_runs_agree_and_a_pair_alone_gives_its_bits_in_the_batch():
 
 def test_the_entry_refuses_what_it_does_not_support():
     from egorear_amd import hip
-    rec = TT.records(TT.rig()).to(DEV)
+    rec = FS.records(FS.rig()).to(DEV)
     cand, cscore = torch.zeros(1, 4, 2, 3, 2, device=DEV), torch.ones(1, 4, 2, 3, device=DEV)
     cindex = torch.zeros(1, 4, 2, 3, dtype=torch.int32, device=DEV)
     out = (torch.empty(1, 4, 2, dtype=torch.int32, device=DEV), torch.empty(1, 4, 2, 2, device=DEV), torch.empty(1, 4, 2, device=DEV),
@@ -162,7 +162,7 @@ def support(p, cand, cscore, cindex, rec, ctm):
     exists = RS.candidates_exist(cand, cscore, cindex)
     zero = torch.zeros_like(cscore)
     xy = torch.where(exists.unsqueeze(-1), cand, torch.zeros_like(cand))
-    proj = RS.project_to(p, rec, None if ctm is None else ctm.to(p.dtype), 1.0 / HM, 1.0 / HM)
+    proj = FS.project(p, rec, None if ctm is None else ctm.to(p.dtype), 1.0 / HM, 1.0 / HM)
     keep = 1.0 - ((proj.unsqueeze(3) - xy) ** 2).sum(-1) / (TAU * TAU)
     best = torch.where(exists & (keep > 0), torch.where(exists, cscore, zero) * keep, zero).max(-1)[0]      # (B, V, J): 0 = no support
     return best.sum(1), (best > 0).sum(1).to(torch.int32)
@@ -180,12 +180,12 @@ def test_the_winning_hypothesis_scores_what_its_triangulated_point_scores(shape)
     from egorear_amd import hip
     B, V, J, K, rw = shape
     g = torch.Generator().manual_seed(7000 + 100 * V + 10 * K + int(rw))
-    cams = TT.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
-    rec = TT.records(cams)
-    ctm = TT.random_ctm(B, V, cams, g) if rw else None
-    true = (TT.project(TT.random_points(B, J, g), rec, ctm) * HM).float()
+    cams = FS.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
+    rec = FS.records(cams)
+    ctm = FS.random_ctm(B, V, cams, g) if rw else None
+    true = (FS.project(FS.random_points(B, J, g), rec, ctm) * HM).float()
     cand, cscore, cindex, mv = make_case("projected", shape, g, true)
-    assert float(cscore.min()) >= TT.THR                                               # every candidate's view counts in the triangulation
+    assert float(cscore.min()) >= FS.THR                                               # every candidate's view counts in the triangulation
     f64 = RS.consensus_statement(cand.double(), cscore.double(), cindex, rec, ctm, 1.0 / HM, 1.0 / HM, TAU, mv)
     f32 = RS.consensus_statement(cand, cscore, cindex, rec, ctm, 1.0 / HM, 1.0 / HM, TAU, mv)
     sure = RS.decided(f64)
@@ -203,13 +203,14 @@ def test_the_winning_hypothesis_scores_what_its_triangulated_point_scores(shape)
             (va, vb), ka, kb = pairs[h // (K * K)], (h // K) % K, h % K
             for v, k in ((va, ka), (vb, kb)):
                 coords[b, v, j], conf[b, v, j] = cand[b, v, j, k], cscore[b, v, j, k]
-    pts, _, _, ok = (t.cpu() for t in TT.launch(d, coords, conf))
+    pts, _, _, ok = (t.cpu() for t in hip.triangulate(coords.to(DEV), conf.to(DEV), rec.to(DEV), None if ctm is None else ctm.to(DEV),
+                                                        1.0 / HM, 1.0 / HM, FS.THR, FS.MIN_DET))
     assert bool(ok.all()), shape
     want, views = support(pts.double(), cand.double(), cscore.double(), cindex, rec, ctm)
     print(f"{shape}: hypotheses {sorted(set(hyp.view(-1).tolist()))}, inliers {sorted(set(inliers.view(-1).tolist()))}")
     assert torch.equal(inliers, views), shape
     own = f32["all_score"].gather(2, f64["hyp"].long().unsqueeze(-1)).squeeze(-1)
-    err, allowed = TT.yardstick("score", score[sure], own[sure], want[sure])
+    err, allowed = FS.yardstick("score", score[sure], own[sure], want[sure])
     assert err <= allowed, (shape, err, allowed)
 
 
@@ -241,7 +242,7 @@ def test_robust_chain_on_the_distractor_scene(scene):
     assert torch.equal(con.choice.cpu(), con64["choice"]) and torch.equal(con.hypothesis.cpu(), con64["hyp"])
     assert torch.equal(con.inliers.cpu(), con64["inliers"]) and bool((con.inliers == 4).all())
     assert torch.equal(peaks.index.cpu(), peaks64[2]) and torch.equal(peaks.count.cpu(), peaks64[3])
-    err, allowed = TT.yardstick("pose", rob.pose, scene["f32"][0], p64)
+    err, allowed = FS.yardstick("pose", rob.pose, scene["f32"][0], p64)
     assert err <= allowed, (err, allowed)
     # the residual reports the accepted views, which here are all four; the distractor view's own top-1 peak is not among them
     assert float(rob.residual.max()) < 15.0 and bool((con.conf > 0.5).all())

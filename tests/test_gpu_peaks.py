@@ -1,12 +1,12 @@
 """Multi-peak heat-map decoding on the GPU (egr_peaks_f32, egorear_amd/decode.py) against the float64 statement of
 tests/robust_statement.py.  `index`, `count` and `score` rest on exact fp32 comparisons and copies: they must equal the statement's.
-`coords` meet the yardstick of test_gpu_triangulate.py: at most 8 x the deviation of torch's fp32 CPU evaluation of the statement from
+`coords` meet the yardstick of fisheye_statement.py: at most 8 x the deviation of torch's fp32 CPU evaluation of the statement from
 its float64 evaluation - per case, printed - with a floor of 4 fp32 ulp of the largest coordinate."""
 import pytest
 import torch
 
 import robust_statement as RS
-import test_gpu_triangulate as TT
+from fisheye_statement import yardstick
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -87,7 +87,7 @@ def test_peaks_against_the_float64_statement(shape):
         assert torch.equal(count.cpu(), f64[3]), (shape, case)
         assert torch.equal(score.cpu().double(), f64[1]), (shape, case)                   # the peak's own value, copied
         assert torch.equal(f32[2], f64[2]) and torch.equal(f32[3], f64[3])                # (fp32 comparisons are exact in either)
-        err, allowed = TT.yardstick("coords", coords, f32[0], f64[0])
+        err, allowed = yardstick("coords", coords, f32[0], f64[0])
         if not err <= allowed:
             bad.append((shape, case, err, allowed))
         empty = (f64[2] < 0)

@@ -1,7 +1,7 @@
 """The bone-length-constrained skeleton fit on the GPU (egr_skeleton_fit_f32, egr_bone_lengths_f32, egr_skeleton_resize_f32,
 egorear_amd/decode.py) against the statements of tests/skeleton_statement.py.
 
-Yardstick: test_gpu_triangulate's - a HIP output may deviate from the float64 statement (on the same fp32 inputs) by at most MARGIN = 8 x
+Yardstick: fisheye_statement's - a HIP output may deviate from the float64 statement (on the same fp32 inputs) by at most MARGIN = 8 x
 the deviation of the float32 evaluation of that statement, with a floor of 4 ulp (fp32) of the output's largest magnitude.
 
 The binding check is solver-independent: at the returned fp32 pose the float64 gradient g and exact Hessian H of the energy (autograd of
@@ -15,12 +15,12 @@ tension / length, is not small against the rays' stiffness along the viewing dir
 import pytest
 import torch
 
+import fisheye_statement as FS
 import skeleton_statement as SS
-import test_gpu_triangulate as TT
 
 pytestmark = pytest.mark.gpu
-DEV = TT.DEV
-MARGIN = TT.MARGIN
+DEV = "cuda:0"
+MARGIN = FS.MARGIN
 ITERATIONS = 176
 # (B, V, J, rw, chain): the 15-joint tree; a chain on the front pair; one bone; the 16-joint tree on rw with per-frame lengths; no bone
 SHAPES = [(3, 4, 15, False, False), (2, 2, 5, False, True), (1, 3, 2, False, False), (2, 4, 16, True, False), (1, 4, 1, False, False)]
@@ -55,7 +55,7 @@ def launch(shape, ops, lam, iterations=ITERATIONS):
     sc = scene(shape)
     ctm = None if sc["ctm"] is None else sc["ctm"].to(DEV)
     out = hip.skeleton_fit(ops["coords"].to(DEV), ops["conf"].to(DEV), sc["rec"].to(DEV), ctm, sc["parents"], ops["bone_length"].to(DEV),
-                           ops["init"].to(DEV), ops["init_ok"].to(DEV), 1.0 / SS.HM, 1.0 / SS.HM, TT.THR, TT.MIN_DET, lam, ops["rho"], iterations)
+                           ops["init"].to(DEV), ops["init_ok"].to(DEV), 1.0 / SS.HM, 1.0 / SS.HM, FS.THR, FS.MIN_DET, lam, ops["rho"], iterations)
     torch.cuda.synchronize()
     return dict(zip(("pose", "ray_cost", "bone", "valid", "energy0", "energy", "grad", "steps"), (t.cpu() for t in out)))
 
@@ -79,7 +79,7 @@ def test_against_the_statement_and_stationary(shape, case):
         for name in ("pose", "ray_cost", "bone", "energy0", "energy"):
             keep = {"pose": fixed.unsqueeze(-1), "bone": fixed_bone}.get(name)
             pick = (lambda t: t) if keep is None else (lambda t: torch.where(keep, t, torch.zeros_like(t)))
-            err, allowed = TT.yardstick(name, pick(got[name]), pick(f32[name]), pick(f64[name]))
+            err, allowed = FS.yardstick(name, pick(got[name]), pick(f32[name]), pick(f64[name]))
             if not err <= allowed:
                 bad.append((shape, case, lam, name, err, allowed))
         # stationarity of the returned pose, and the kernel's own report of it
@@ -115,13 +115,13 @@ def monotone(shape, ops, lam, got):
     start, pose = pr.start(), got["pose"].double()
     E_start, E_pose = SS.energy(pr, start)[0], SS.energy(pr, pose)[0]
     g, H = SS.grad_hess(pr, pose)
-    h = SS.ulp32(float(pose.abs().max())) / 2.0
+    h = FS.ulp32(float(pose.abs().max())) / 2.0
     cost = 2.0 * (g.abs().sum(1) * h + 0.5 * H.abs().sum((1, 2)) * h * h)
     print(f"    E(start) {E_start.tolist()} -> E(pose) {E_pose.tolist()} (float64 at the returned pose; rounding may cost {cost.tolist()}), "
           f"outputs {got['energy0'].tolist()} -> {got['energy'].tolist()}, steps {got['steps'].tolist()}")
     assert bool((E_pose <= E_start + cost).all()), (shape, lam, E_start.tolist(), E_pose.tolist())
-    ulp0 = torch.tensor([SS.ulp32(float(e)) for e in E_start], dtype=torch.float64)
-    ulp1 = torch.tensor([SS.ulp32(float(e)) for e in E_pose], dtype=torch.float64)
+    ulp0 = torch.tensor([FS.ulp32(float(e)) for e in E_start], dtype=torch.float64)
+    ulp1 = torch.tensor([FS.ulp32(float(e)) for e in E_pose], dtype=torch.float64)
     assert bool(((got["energy0"].double() - E_start).abs() <= 4.0 * ulp0).all())
     assert bool(((got["energy"].double() - E_pose).abs() <= cost + 4.0 * ulp1).all())
     assert bool((got["energy"].double() <= got["energy0"].double() + ulp0).all())
@@ -157,22 +157,22 @@ def test_without_bones_and_prior_it_is_the_triangulation(shape):
         got = launch(shape, ops, 0.0)
         ctm = None if sc["ctm"] is None else sc["ctm"].to(DEV)
         pts, cost, _, ok = (t.cpu() for t in hip.triangulate(ops["coords"].to(DEV), ops["conf"].to(DEV), sc["rec"].to(DEV), ctm, 1.0 / SS.HM,
-                                                             1.0 / SS.HM, TT.THR, TT.MIN_DET))
+                                                             1.0 / SS.HM, FS.THR, FS.MIN_DET))
         keep = ok.bool() & ops["init_ok"].bool() & torch.isfinite(ops["init"]).all(-1)
         assert int(keep.sum()) > 0 or shape[2] <= 2
         assert bool(got["valid"].bool()[keep].all())
-        f64 = TT.statement(ops["coords"].double(), ops["conf"].double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
-        f32 = TT.statement(ops["coords"], ops["conf"], sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
+        f64 = FS.statement(ops["coords"].double(), ops["conf"].double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
+        f32 = FS.statement(ops["coords"], ops["conf"], sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
         print(f"{shape} {case}: {int(keep.sum())} triangulated joints")
         if int(keep.sum()) == 0:
             continue
         for name, mine, theirs, i in (("pose", got["pose"], pts, 0), ("ray_cost", got["ray_cost"], cost, 1)):
             for what, value in (("fit", mine), ("triangulate", theirs)):                # both launches against the one statement
-                err, allowed = TT.yardstick(f"{name} ({what})", value[keep], f32[i][keep], f64[i][keep])
+                err, allowed = FS.yardstick(f"{name} ({what})", value[keep], f32[i][keep], f64[i][keep])
                 if not err <= allowed:
                     bad.append((shape, case, name, what, err, allowed))
             err = float((mine.double() - theirs.double())[keep].abs().max())
-            _, allowed = TT.yardstick(f"{name} (fit against triangulate)", mine[keep], f32[i][keep], f64[i][keep])
+            _, allowed = FS.yardstick(f"{name} (fit against triangulate)", mine[keep], f32[i][keep], f64[i][keep])
             if not err <= allowed:
                 bad.append((shape, case, name, "difference", err, allowed))
     assert not bad, bad
@@ -191,7 +191,7 @@ def test_a_joint_one_camera_sees_is_placed(shape):
         ref = reference(shape, "one_view", lam)
         ops = ref["ops"]
         ctm = None if sc["ctm"] is None else sc["ctm"].to(DEV)
-        ok = hip.triangulate(ops["coords"].to(DEV), ops["conf"].to(DEV), sc["rec"].to(DEV), ctm, 1.0 / SS.HM, 1.0 / SS.HM, TT.THR, TT.MIN_DET)[3]
+        ok = hip.triangulate(ops["coords"].to(DEV), ops["conf"].to(DEV), sc["rec"].to(DEV), ctm, 1.0 / SS.HM, 1.0 / SS.HM, FS.THR, FS.MIN_DET)[3]
         assert int(ok[:, leaf].sum()) == 0
         got = launch(shape, ops, lam)
         assert bool(got["valid"][:, leaf].all())
@@ -207,7 +207,7 @@ def test_a_joint_one_camera_sees_is_placed(shape):
         truth = sc["pts"][:, leaf]
         mine = (got["pose"][:, leaf].double() - truth).norm(dim=-1)
         theirs = (referee[:, leaf] - truth).norm(dim=-1)
-        err, allowed = TT.yardstick("the one-view joint", got["pose"][:, leaf], ref["f32"]["pose"][:, leaf], referee[:, leaf])
+        err, allowed = FS.yardstick("the one-view joint", got["pose"][:, leaf], ref["f32"]["pose"][:, leaf], referee[:, leaf])
         print(f"{shape} lambda {lam}: distance from the true joint: fit {mine.tolist()} cm, referee {theirs.tolist()} cm")
         assert err <= allowed and bool((mine <= theirs + allowed).all())
 
@@ -219,7 +219,7 @@ def test_bits_do_not_depend_on_the_batch_the_run_or_a_graph_replay():
     ops = SS.case_operands(sc, "one_view")
     rec, L = sc["rec"].to(DEV), ops["bone_length"].to(DEV)
     c, w, q, k = ops["coords"].to(DEV), ops["conf"].to(DEV), ops["init"].to(DEV), ops["init_ok"].to(DEV)
-    run = lambda cc, ww, qq, kk: hip.skeleton_fit(cc, ww, rec, None, sc["parents"], L, qq, kk, 1.0 / SS.HM, 1.0 / SS.HM, TT.THR, TT.MIN_DET, 10.0,
+    run = lambda cc, ww, qq, kk: hip.skeleton_fit(cc, ww, rec, None, sc["parents"], L, qq, kk, 1.0 / SS.HM, 1.0 / SS.HM, FS.THR, FS.MIN_DET, 10.0,
                                                   1e-3, 48)
     eager, again = run(c, w, q, k), run(c, w, q, k)
     for a, b in zip(eager, again):
@@ -262,12 +262,12 @@ def test_the_small_launches_against_their_statements(B):
     assert torch.equal(count, c64) and int(count[14]) == 0 and float(length[14]) == 0.0 and float(length[0]) == 0.0
     bad = []
     for name, got, f32, f64 in (("length", length, l32, l64), ("spread", spread, s32, s64)):
-        err, allowed = TT.yardstick(name, got, f32, f64)
+        err, allowed = FS.yardstick(name, got, f32, f64)
         if not err <= allowed:
             bad.append((name, err, allowed))
     for table in (L, L.expand(B, 15).contiguous()):
         out = hip.skeleton_resize(pose.to(DEV), valid.to(DEV), table.to(DEV), parents).cpu()
-        err, allowed = TT.yardstick("resize", out, SS.resize_statement(pose, valid, table, parents),
+        err, allowed = FS.yardstick("resize", out, SS.resize_statement(pose, valid, table, parents),
                                     SS.resize_statement(pose.double(), valid, table.double(), parents))
         if not err <= allowed:
             bad.append(("resize", err, allowed))
@@ -280,8 +280,8 @@ def test_the_small_launches_against_their_statements(B):
         used = ~keep & (L > 0).unsqueeze(0)
         got_len = (out.double() - out.double()[:, list(parents)]).norm(dim=-1)
         off = float((got_len - L.double().unsqueeze(0))[used].abs().max())
-        print(f"B {B}: {int(used.sum())} rescaled bones, largest |length - L| {off:.3e} cm, 4 ulp32 {4 * SS.ulp32(float(out.abs().max())):.3e}")
-        assert int(used.sum()) > 0 and off <= 4 * SS.ulp32(float(out.abs().max()))
+        print(f"B {B}: {int(used.sum())} rescaled bones, largest |length - L| {off:.3e} cm, 4 ulp32 {4 * FS.ulp32(float(out.abs().max())):.3e}")
+        assert int(used.sum()) > 0 and off <= 4 * FS.ulp32(float(out.abs().max()))
     assert torch.equal(hip.bone_lengths(pose.to(DEV), valid.to(DEV), parents)[0].cpu(), length)               # the same bits again
     assert not bad, bad
 
@@ -291,15 +291,10 @@ def bump_maps():
     """Gaussian bumps (sigma 1, 64 x 64) at the projections of a 15-joint skeleton, B = 2, V = 4, on the syn rig (the fixture style of
     test_gpu_triangulate.bump_maps)."""
     g = torch.Generator().manual_seed(78)
-    cams = TT.rig()
-    rec = TT.records(cams)
-    parents = SS.parents_15()
-    pts, lengths = SS.random_skeleton(2, 15, parents, g)
-    centre = TT.project(pts, rec, None) * SS.HM
-    xs = torch.arange(SS.HM, dtype=torch.float64).view(1, 1, 1, 1, SS.HM)
-    ys = torch.arange(SS.HM, dtype=torch.float64).view(1, 1, 1, SS.HM, 1)
-    hm = torch.exp(-((xs - centre[..., 0, None, None]) ** 2 + (ys - centre[..., 1, None, None]) ** 2) / 2.0)
-    return {"cams": cams, "rec": rec, "pts": pts, "lengths": lengths.float(), "hm": hm.float().contiguous()}
+    cams = FS.rig()
+    rec = FS.records(cams)
+    pts, lengths = SS.random_skeleton(2, 15, SS.parents_15(), g)
+    return {"cams": cams, "rec": rec, "pts": pts, "lengths": lengths.float(), "hm": FS.bumps(pts, rec, None, SS.HM, SS.HM).float().contiguous()}
 
 
 def test_decode_joints_3d_skeleton_on_rendered_bumps(bump_maps):
@@ -341,5 +336,5 @@ def test_bad_launches_are_refused():
     for kw in (args(parents=[0, 1]), args(parents=[1, 0]), args(lam=-1.0), args(rho=float("nan")), args(iterations=0), args(iterations=257)):
         with pytest.raises(ValueError):
             hip.skeleton_fit(ops["coords"].to(DEV), ops["conf"].to(DEV), sc["rec"].to(DEV), None, kw["parents"], ops["bone_length"].to(DEV),
-                             ops["init"].to(DEV), ops["init_ok"].to(DEV), 1.0 / SS.HM, 1.0 / SS.HM, TT.THR, TT.MIN_DET, kw["lam"], kw["rho"],
+                             ops["init"].to(DEV), ops["init_ok"].to(DEV), 1.0 / SS.HM, 1.0 / SS.HM, FS.THR, FS.MIN_DET, kw["lam"], kw["rho"],
                              kw["iterations"])

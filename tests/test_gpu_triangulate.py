@@ -1,152 +1,22 @@
-"""Fisheye triangulation on the GPU (egr_triangulate_f32 / egr_triangulate_bwd_f32, egorear_amd/decode.py) against a float64 statement
-of its math written here in elementwise torch operations: ray by Newton to convergence, the normal equations, a closed-form symmetric
-solve, the cost and the ray distances.  torch.autograd differentiates the statement; no LAPACK call is involved.
+"""Fisheye triangulation on the GPU (egr_triangulate_f32 / egr_triangulate_bwd_f32, egorear_amd/decode.py) against the float64
+statement of its math in tests/fisheye_statement.py, in elementwise torch operations: ray by Newton to convergence, the normal equations,
+a closed-form symmetric solve, the cost and the ray distances.  torch.autograd differentiates the statement; no LAPACK call is involved.
 
-The yardstick is the one of test_gpu_soft_argmax.py: a HIP output or gradient may deviate from the float64 statement (evaluated on the
-same fp32 inputs) by at most 8 x the deviation of torch's fp32 CPU evaluation of that statement - computed per case and printed next to
+The yardstick (fisheye_statement.yardstick) is the one of test_gpu_soft_argmax.py: a HIP output or gradient may deviate from the
+float64 statement (evaluated on the same fp32 inputs) by at most 8 x the deviation of torch's fp32 CPU evaluation of that statement - computed per case and printed next to
 the HIP figure - with a floor of 4 ulp (fp32) of the output's largest magnitude for the cases where the fp32 evaluation is exact."""
-import math
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from fisheye_statement import (HM, MARGIN, MIN_DET, THR, bumps, project, random_ctm, random_points, records, rig, soft_argmax_statement,
+                               statement, ulp32, yardstick)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-MARGIN = 8.0
-THR = 0.5
-MIN_DET = 1e-6
-HM = 64                                       # heat-map side: coords are pixels of a 64 x 64 map
-NAMES = ("camera_front_left", "camera_front_right", "camera_back_left", "camera_back_right")
 # (B, V, J, rw): the product layout on the syn rig; the two front cameras; one pair; rw with a per-sample coord_trans_mat
 SHAPES = [(4, 4, 15, False), (3, 2, 5, False), (1, 3, 1, False), (5, 4, 16, True)]
 CASES = ("ones", "noisy", "dropped", "nan")
-
-
-def rig(model="ego4view_syn"):
-    from egorear_amd.camera import FishEyeCameraCalibratedModel
-    calib = os.path.join(os.path.dirname(os.path.abspath(__import__("egorear_amd").__file__)), "calib", "ego4view")
-    return [FishEyeCameraCalibratedModel(model, calib, n) for n in NAMES]
-
-
-def records(cams):
-    return torch.from_numpy(np.stack([c.packed_rays() for c in cams]))
-
-
-# --------------------------------------------------------------------------- the statement
-
-def _poly(coef, x, n):
-    """sum_i coef[..., i] x^i by Horner; coef (V, n) against x (B, V, J)."""
-    acc = torch.zeros_like(x)
-    for i in range(n - 1, -1, -1):
-        acc = acc * x + coef[:, i].view(1, -1, 1)
-    return acc
-
-
-def _dpoly(coef, x, n):
-    acc = torch.zeros_like(x)
-    for i in range(n - 1, 0, -1):
-        acc = acc * x + i * coef[:, i].view(1, -1, 1)
-    return acc
-
-
-def extrinsics(rec, ctm, B, V, dt):
-    """R[r][c], t[r] broadcastable to (B, V, J): p_cam = R p + t in cm.  syn (ctm None): each camera on its own, R = diag(f, f, 1)."""
-    if ctm is not None:
-        m = ctm.to(dt)
-        return [[m[:, :, r, c].unsqueeze(-1) for c in range(3)] for r in range(3)], [100.0 * m[:, :, r, 3].unsqueeze(-1) for r in range(3)]
-    rec = rec.to(dt)
-    f = torch.where(rec[:, 26] != 0, -torch.ones_like(rec[:, 26]), torch.ones_like(rec[:, 26])).view(1, V, 1)
-    z, o = torch.zeros_like(f), torch.ones_like(f)
-    return [[f, z, z], [z, f, z], [z, z, o]], [rec[:, 27 + r].view(1, V, 1) for r in range(3)]
-
-
-def statement(coords, conf, rec, ctm, sx, sy, thr=THR, min_det_ratio=MIN_DET, newton=6):
-    """coords (B, V, J, 2), conf (B, V, J) in their own dtype (float64 or float32); rec (V, 30) = camera.packed_rays(); ctm (B, V, 4, 4)
-    or None -> pts (B, J, 3), cost (B, J), resid (B, V, J), ok (B, J) bool."""
-    dt = coords.dtype
-    B, V, J = conf.shape
-    c = rec.to(dt)
-    x, y = coords[..., 0], coords[..., 1]
-    use = (conf >= thr) & (conf > 0) & torch.isfinite(conf) & torch.isfinite(x) & torch.isfinite(y)
-    zero = torch.zeros_like(conf)
-    # (an excluded view weighs 0; its coordinates are replaced by the middle of the image so that 0 * its ray stays finite)
-    w, x, y = torch.where(use, conf, zero), torch.where(use, x, zero + 0.5 / sx), torch.where(use, y, zero + 0.5 / sy)
-    col = lambda i: c[:, i].view(1, V, 1)
-    dx, dy = x * sx * col(3) - col(1), y * sy * col(4) - col(2)
-    rho = torch.sqrt(dx * dx + dy * dy)
-    axis = ~(rho >= 1e-4)
-    rs = torch.where(axis, torch.ones_like(rho), rho)
-    ux, uy = torch.where(axis, zero, dx / rs), torch.where(axis, zero, dy / rs)
-    theta = torch.atan(_poly(c[:, 18:26], rs, 8) / rs)
-    for _ in range(newton):
-        theta = theta - (_poly(c[:, 5:17], theta, 12) - rs) / _dpoly(c[:, 5:17], theta, 12)
-    st, ct = torch.where(axis, -torch.ones_like(rho), torch.sin(theta)), torch.where(axis, zero, torch.cos(theta))
-    d = [ux * ct, uy * ct, -st]
-    R, t = extrinsics(rec, ctm, B, V, dt)
-    e = [sum(R[r][k] * d[r] for r in range(3)) for k in range(3)]
-    rt = [sum(R[r][k] * t[r] for r in range(3)) for k in range(3)]
-    d_t = sum(d[r] * t[r] for r in range(3))
-    A = {(k, l): (w * (sum(R[r][k] * R[r][l] for r in range(3)) - e[k] * e[l])).sum(1) for k in range(3) for l in range(k, 3)}
-    b = [-(w * (rt[k] - e[k] * d_t)).sum(1) for k in range(3)]
-    a00, a01, a02, a11, a12, a22 = A[0, 0], A[0, 1], A[0, 2], A[1, 1], A[1, 2], A[2, 2]
-    c00, c01, c02 = a11 * a22 - a12 * a12, a02 * a12 - a01 * a22, a01 * a12 - a02 * a11
-    c11, c12, c22 = a00 * a22 - a02 * a02, a01 * a02 - a00 * a12, a00 * a11 - a01 * a01
-    det = a00 * c00 + a01 * c01 + a02 * c02
-    tr3 = (a00 + a11 + a22) / 3
-    ok = ((w > 0).sum(1) >= 2) & (det > min_det_ratio * tr3 * tr3 * tr3)
-    ds = torch.where(ok, det, torch.ones_like(det))
-    zj = torch.zeros_like(det)
-    p = [torch.where(ok, (c00 * b[0] + c01 * b[1] + c02 * b[2]) / ds, zj), torch.where(ok, (c01 * b[0] + c11 * b[1] + c12 * b[2]) / ds, zj),
-         torch.where(ok, (c02 * b[0] + c12 * b[1] + c22 * b[2]) / ds, zj)]
-    q = [sum(R[r][k] * p[k].unsqueeze(1) for k in range(3)) + t[r] for r in range(3)]
-    dq = sum(d[r] * q[r] for r in range(3))
-    rr = sum((q[r] - d[r] * dq) ** 2 for r in range(3))
-    keep = use & ok.unsqueeze(1)
-    wsum = torch.where(ok, w.sum(1), torch.ones_like(det))
-    cost = torch.where(ok, (w * rr).sum(1) / wsum, zj)
-    resid = torch.sqrt(torch.where(keep, rr, zero))
-    return torch.stack(p, -1), cost, resid, ok
-
-
-def project(pts, rec, ctm):
-    """float64 restatement of world2camera_pytorch for one camera at a time (un-chained, unclamped): pts (B, J, 3) cm -> the
-    normalised image points (B, V, J, 2)."""
-    B, J, _ = pts.shape
-    V = rec.shape[0]
-    c = rec.double()
-    R, t = extrinsics(rec, ctm, B, V, torch.float64)
-    p = [pts[..., k].unsqueeze(1) for k in range(3)]
-    q = [sum(R[r][k] * p[k] for k in range(3)) + t[r] for r in range(3)]
-    norm = torch.sqrt(q[0] * q[0] + q[1] * q[1])
-    theta = torch.atan(-q[2] / norm)
-    rho = _poly(c[:, 5:17], theta, 12)
-    u = (q[0] / norm * rho + c[:, 1].view(1, V, 1)) / c[:, 3].view(1, V, 1)
-    v = (q[1] / norm * rho + c[:, 2].view(1, V, 1)) / c[:, 4].view(1, V, 1)
-    return torch.stack((u, v), -1)
-
-
-def random_points(B, J, g):
-    r = torch.rand(B, J, 3, generator=g, dtype=torch.float64)
-    return torch.stack((r[..., 0] * 120 - 60, r[..., 1] * 120 - 40, r[..., 2] * 135 + 15), -1)
-
-
-def random_ctm(B, V, cams, g):
-    """Per sample a rotation of at most 0.05 rad about a random axis, composed with each camera's nominal pose; translations in m."""
-    ax = torch.randn(B, 3, generator=g, dtype=torch.float64)
-    ax = ax / ax.norm(dim=1, keepdim=True)
-    ang = (torch.rand(B, generator=g, dtype=torch.float64) - 0.5) * 0.1
-    K = torch.zeros(B, 3, 3, dtype=torch.float64)
-    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -ax[:, 2], ax[:, 1], ax[:, 2], -ax[:, 0], -ax[:, 1], ax[:, 0]
-    rot = torch.eye(3, dtype=torch.float64) + torch.sin(ang).view(B, 1, 1) * K + (1 - torch.cos(ang)).view(B, 1, 1) * (K @ K)
-    m = torch.zeros(B, V, 4, 4, dtype=torch.float64)
-    for v, cam in enumerate(cams):
-        f = -1.0 if cam.flip_xy else 1.0
-        m[:, v, :3, :3] = torch.diag(torch.tensor([f, f, 1.0], dtype=torch.float64)) @ rot
-        m[:, v, :3, 3] = torch.tensor(cam.offset, dtype=torch.float64) * 0.01
-        m[:, v, 3, 3] = 1.0
-    return m.float().contiguous()
 
 
 # --------------------------------------------------------------------------- data, computed once and shared (never modified)
@@ -197,20 +67,6 @@ def shape_data(shape):
         cases[case] = (coords.contiguous(), conf.contiguous(), thr, evaluate(coords, conf, rec, ctm, 1.0 / HM, 1.0 / HM, g_pts, g_cost, thr))
     _CACHE[shape] = {"cams": cams, "rec": rec, "ctm": ctm, "pts": pts, "g_pts": g_pts, "g_cost": g_cost, "cases": cases}
     return _CACHE[shape]
-
-
-def ulp32(m):
-    return 0.0 if m == 0.0 else 2.0 ** (math.floor(math.log2(m)) - 23)
-
-
-def yardstick(what, got, f32, f64):
-    """(HIP deviation, allowed deviation) of one output against the float64 statement; prints both and the ratio."""
-    f64 = f64.double()
-    err, own = float((got.double().cpu() - f64).abs().max()), float((f32.double() - f64).abs().max())
-    floor = 4.0 * ulp32(float(f64.abs().max()))
-    print(f"    {what}: |hip - f64| {err:.3e}, |torch fp32 - f64| {own:.3e}, ratio {err / own if own else float('inf'):.3g}, "
-          f"4 ulp floor {floor:.3e}, largest entry {float(f64.abs().max()):.4g}")
-    return err, max(MARGIN * own, floor)
 
 
 def launch(d, coords, conf, hm=HM, thr=THR):
@@ -385,15 +241,6 @@ def test_two_runs_and_a_graph_replay_give_the_same_bits():
 
 # --------------------------------------------------------------------------- heat maps to 3-D
 
-def _soft_argmax64(hm, beta):
-    """softmax(beta h)-weighted mean (x, y) and the maximum of maps (..., H, W), in hm's dtype."""
-    H, W = hm.shape[-2:]
-    p = torch.softmax((hm * beta).reshape(hm.shape[:-2] + (H * W,)), dim=-1).reshape(hm.shape)
-    x = (p.sum(-2) * torch.arange(W, dtype=hm.dtype)).sum(-1)
-    y = (p.sum(-1) * torch.arange(H, dtype=hm.dtype)).sum(-1)
-    return torch.stack((x, y), -1), hm.reshape(hm.shape[:-2] + (H * W,)).max(-1)[0]
-
-
 @pytest.fixture(scope="module")
 def bump_maps():
     """Gaussian bumps (sigma 1, 64 x 64) at the projections of known points, B = 2, V = 4, J = 15, on the syn rig."""
@@ -401,10 +248,7 @@ def bump_maps():
     cams = rig()
     rec = records(cams)
     pts = random_points(2, 15, g)
-    centre = project(pts, rec, None) * HM
-    xs, ys = torch.arange(HM, dtype=torch.float64).view(1, 1, 1, 1, HM), torch.arange(HM, dtype=torch.float64).view(1, 1, 1, HM, 1)
-    hm = torch.exp(-((xs - centre[..., 0, None, None]) ** 2 + (ys - centre[..., 1, None, None]) ** 2) / 2.0)
-    return {"cams": cams, "rec": rec, "pts": pts, "hm": hm.float().contiguous()}
+    return {"cams": cams, "rec": rec, "pts": pts, "hm": bumps(pts, rec, None, HM, HM).float().contiguous()}
 
 
 def test_decode_joints_3d_on_rendered_bumps(bump_maps):
@@ -417,8 +261,8 @@ def test_decode_joints_3d_on_rendered_bumps(bump_maps):
     by_name, _ = decode.decode_joints_3d(hm.to(DEV), "ego4view_syn")                  # the packaged calibrations, by camera_model
     assert torch.equal(by_name.pose, tri.pose)
     # the bound: what the float64 statement makes of the float64 soft-argmax of the same maps, plus the yardstick
-    c64, m64 = _soft_argmax64(hm.double(), 100.0)
-    c32, m32 = _soft_argmax64(hm, 100.0)
+    c64, m64 = soft_argmax_statement(hm.double(), 100.0)
+    c32, m32 = soft_argmax_statement(hm, 100.0)
     p64 = statement(c64, m64, rec, None, 1.0 / HM, 1.0 / HM)[0]
     p32 = statement(c32, m32, rec, None, 1.0 / HM, 1.0 / HM)[0]
     decode_err = float((p64 - pts).abs().max())

@@ -1,131 +1,28 @@
-"""Volumetric fusion on the GPU (egr_volume_fuse_f32 / egr_volume_fuse_bwd_f32, egorear_amd/decode.py) against a float64 statement of
-its math written here in elementwise torch operations, with a gather for the bilinear corners: voxel centres, the
-un-chained fisheye projection, zero-padded bilinear samples, the weighted fusion of the views and one 3-D soft-argmax.  torch.autograd
-differentiates the statement.
+"""Volumetric fusion on the GPU (egr_volume_fuse_f32 / egr_volume_fuse_bwd_f32, egorear_amd/decode.py) against the float64 statement of
+its math in tests/volume_statement.py.  torch.autograd differentiates the statement.
 
-The yardstick is the one of test_gpu_soft_argmax.py and test_gpu_triangulate.py: a HIP output or gradient may deviate from the float64
-statement (evaluated on the same fp32 inputs) by at most 8 x the deviation of torch's fp32 CPU evaluation of that statement - taken
-per output kind as the maximum over the cases of one shape, so that one lucky case cannot shrink the allowance - with a floor of 4 ulp
-(fp32) of the output's largest magnitude.  Both figures are printed per case.  `index` is compared exactly on the pairs whose float64
-best and second-best score differ by more than 8 x the fp32 statement's largest score deviation in that case; at most one pair in ten
-of a case may be left out this way, which is checked here on the CPU."""
+The yardstick (fisheye_statement.yardstick, with `shape_own`) is that of test_gpu_soft_argmax.py: a HIP output or gradient may deviate
+from the float64 statement (evaluated on the same fp32 inputs) by at most 8 x the deviation of torch's fp32 CPU evaluation of that
+statement - taken per output kind as the maximum over the cases of one shape, so that one lucky case cannot shrink the allowance -
+with a floor of 4 ulp (fp32) of the output's largest magnitude.  Both figures are printed per case.  `index` is compared exactly on the
+pairs whose float64 best and second-best score differ by more than 8 x the fp32 statement's largest score deviation in that case; at
+most one pair in ten of a case may be left out this way, which is checked here on the CPU."""
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
+from fisheye_statement import MARGIN, THR, bumps, heatmap_coords, random_ctm, random_points, records, rig, ulp32, yardstick
+from volume_statement import offsets, statement
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-MARGIN = 8.0
-THR = 0.5
 CUBE = 40.0
-NAMES = ("camera_front_left", "camera_front_right", "camera_back_left", "camera_back_right")
 # (B, V, J, H, W, G, rw): the product's maps; the smallest, non-square, the two front cameras; an odd grid with lanes that own no voxel;
 # rw with a per-sample coord_trans_mat (rotations up to 0.05 rad); the largest grid
 SHAPES = [(2, 4, 3, 64, 64, 8, False), (1, 2, 1, 16, 12, 4, False), (3, 3, 2, 32, 32, 5, False), (2, 4, 2, 64, 64, 16, True),
           (1, 4, 1, 64, 64, 32, False)]
 CASES = ("bumps", "noise", "dropped", "nan", "border")
-
-
-def rig(model="ego4view_syn"):
-    from egorear_amd.camera import FishEyeCameraCalibratedModel
-    calib = os.path.join(os.path.dirname(os.path.abspath(__import__("egorear_amd").__file__)), "calib", "ego4view")
-    return [FishEyeCameraCalibratedModel(model, calib, n) for n in NAMES]
-
-
-def records(cams):
-    return torch.from_numpy(np.stack([c.packed_rays() for c in cams]))
-
-
-# --------------------------------------------------------------------------- the statement
-
-def extrinsics(rec, ctm, V, dt):
-    """R[r][c], t[r] broadcastable to (B, V, J, N): p_cam = R p + t in cm.  syn (ctm None): each camera on its own, R = diag(f, f, 1)."""
-    if ctm is not None:
-        m = ctm.to(dt)
-        return ([[m[:, :, r, c].view(-1, V, 1, 1) for c in range(3)] for r in range(3)],
-                [100.0 * m[:, :, r, 3].view(-1, V, 1, 1) for r in range(3)])
-    rec = rec.to(dt)
-    f = torch.where(rec[:, 26] != 0, -torch.ones_like(rec[:, 26]), torch.ones_like(rec[:, 26])).view(1, V, 1, 1)
-    z, o = torch.zeros_like(f), torch.ones_like(f)
-    return [[f, z, z], [z, f, z], [z, z, o]], [rec[:, 27 + r].view(1, V, 1, 1) for r in range(3)]
-
-
-def project(p, rec, ctm, H, W):
-    """p (B, 1 | V, J, N, 3) device-frame points, cm -> heat-map coordinates x, y (B, V, J, N) of an (H, W) map and `take`, false where
-    the view gives no sample (the camera centre and the optical axis behind it).  Unclamped, un-chained."""
-    dt = p.dtype
-    V = rec.shape[0]
-    c = rec.to(dt)
-    col = lambda i: c[:, i].view(1, V, 1, 1)
-    R, t = extrinsics(rec, ctm, V, dt)
-    q = [sum(R[r][k] * p[..., k] for k in range(3)) + t[r] for r in range(3)]
-    n = torch.sqrt(q[0] * q[0] + q[1] * q[1])
-    theta = torch.atan2(-q[2], n)
-    rho, pw = torch.zeros_like(theta), torch.ones_like(theta)
-    for i in range(12):                        # rho = sum_i a_i theta^i, left to right (slots past npoly hold 0)
-        rho = rho + col(5 + i) * pw
-        pw = pw * theta
-    on_axis = n == 0
-    ns = torch.where(on_axis, torch.ones_like(n), n)
-    ex, ey = torch.where(on_axis, torch.zeros_like(n), q[0] / ns), torch.where(on_axis, torch.zeros_like(n), q[1] / ns)
-    x = (ex * rho + col(1)) * W / col(3)
-    y = (ey * rho + col(2)) * H / col(4)
-    return x, y, ~(on_axis & (q[2] <= 0))
-
-
-def offsets(G, cube, dt):
-    """o_i (N, 3) of voxel i = (iz * G + iy) * G + ix."""
-    k = ((torch.arange(G, dtype=dt) + 0.5) / G - 0.5) * cube
-    return torch.stack((k.repeat(G * G), k.repeat_interleave(G).repeat(G), k.repeat_interleave(G * G)), -1)
-
-
-def statement(hm, conf, centers, rec, ctm, G, cube, beta, thr, center_ok=None):
-    """hm (B, V, J, H, W), conf (B, V, J), centers (B, J, 3) in hm's dtype (float64 or float32); rec (V, 30) = camera.packed_rays(); ctm
-    (B, V, 4, 4) or None -> dict(pose (B, J, 3), peak, index, spread, valid (B, J), S (B, J, N), partial = share of the voxel-view
-    samples that miss at least one corner)."""
-    dt = hm.dtype
-    B, V, J, H, W = hm.shape
-    zero = torch.zeros_like(conf)
-    use = (conf >= thr) & (conf > 0) & torch.isfinite(conf)
-    w = torch.where(use, conf, zero)
-    valid = (use.sum(1) >= 2) & torch.isfinite(centers).all(-1)
-    if center_ok is not None:
-        valid = valid & center_ok.bool()
-    c = torch.where(valid.unsqueeze(-1), centers, torch.zeros_like(centers))
-    o = offsets(G, cube, dt)
-    p = c.view(B, 1, J, 1, 3) + o
-    x, y, take = project(p, rec, ctm, H, W)
-    inside = take & (x > -1) & (x < W) & (y > -1) & (y < H)                    # (a NaN fails every comparison)
-    xs, ys = torch.where(inside, x, torch.zeros_like(x)), torch.where(inside, y, torch.zeros_like(y))
-    xf, yf = torch.floor(xs), torch.floor(ys)
-    fx, fy = xs - xf, ys - yf
-    x0, y0 = xf.long(), yf.long()
-    flat = hm.reshape(B, V, J, H * W)
-    corner, whole = {}, inside.clone()
-    for dx in (0, 1):
-        for dy in (0, 1):
-            xi, yi = x0 + dx, y0 + dy
-            there = inside & (xi >= 0) & (xi <= W - 1) & (yi >= 0) & (yi <= H - 1)
-            whole = whole & there
-            got = torch.gather(flat, -1, yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1))
-            corner[dx, dy] = torch.where(there, got, torch.zeros_like(got))       # a corner outside the map counts 0
-    top = corner[0, 0] + fx * (corner[1, 0] - corner[0, 0])
-    bot = corner[0, 1] + fx * (corner[1, 1] - corner[0, 1])
-    s = top + fy * (bot - top)                                                     # (B, V, J, N)
-    wsum = torch.where(valid, w.sum(1), torch.ones_like(w.sum(1)))
-    S = (w.unsqueeze(-1) * s).sum(1) / wsum.unsqueeze(-1)                          # (B, J, N)
-    peak, index = S.max(-1)                                                        # (the first of equal maxima)
-    P = torch.softmax(beta * S, -1)
-    off = (P.unsqueeze(-1) * o).sum(-2)
-    spread = torch.sqrt((P * ((o - off.unsqueeze(-2)) ** 2).sum(-1)).sum(-1))
-    zj = torch.zeros_like(peak)
-    return {"pose": torch.where(valid.unsqueeze(-1), c + off, torch.zeros_like(off)), "peak": torch.where(valid, peak, zj),
-            "index": torch.where(valid, index, torch.full_like(index, -1)), "spread": torch.where(valid, spread, zj), "valid": valid,
-            "S": S.detach(), "partial": float((inside & ~whole)[use].float().mean()) if bool(use.any()) else 0.0,
-            "sampled": float(whole[use].float().mean()) if bool(use.any()) else 0.0}
 
 
 def evaluate(hm, conf, centers, rec, ctm, G, cube, beta, thr, g_pose, g_peak, center_ok=None):
@@ -142,36 +39,6 @@ def evaluate(hm, conf, centers, rec, ctm, G, cube, beta, thr, g_pose, g_peak, ce
     out["decided"] = ((top2[..., 0] - top2[..., 1]) > MARGIN * s_dev) | ~out["f64"]["valid"]
     out["s_dev"] = s_dev
     return out
-
-
-def random_points(B, J, g):
-    r = torch.rand(B, J, 3, generator=g, dtype=torch.float64)
-    return torch.stack((r[..., 0] * 120 - 60, r[..., 1] * 120 - 40, r[..., 2] * 135 + 15), -1)
-
-
-def random_ctm(B, V, cams, g):
-    """Per sample a rotation of at most 0.05 rad about a random axis, composed with each camera's nominal pose; translations in m."""
-    ax = torch.randn(B, 3, generator=g, dtype=torch.float64)
-    ax = ax / ax.norm(dim=1, keepdim=True)
-    ang = (torch.rand(B, generator=g, dtype=torch.float64) - 0.5) * 0.1
-    K = torch.zeros(B, 3, 3, dtype=torch.float64)
-    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -ax[:, 2], ax[:, 1], ax[:, 2], -ax[:, 0], -ax[:, 1], ax[:, 0]
-    rot = torch.eye(3, dtype=torch.float64) + torch.sin(ang).view(B, 1, 1) * K + (1 - torch.cos(ang)).view(B, 1, 1) * (K @ K)
-    m = torch.zeros(B, V, 4, 4, dtype=torch.float64)
-    for v, cam in enumerate(cams):
-        f = -1.0 if cam.flip_xy else 1.0
-        m[:, v, :3, :3] = torch.diag(torch.tensor([f, f, 1.0], dtype=torch.float64)) @ rot
-        m[:, v, :3, 3] = torch.tensor(cam.offset, dtype=torch.float64) * 0.01
-        m[:, v, 3, 3] = 1.0
-    return m.float().contiguous()
-
-
-def bumps(pts, rec, ctm, H, W, height=1.0):
-    """Gaussian bumps (sigma 1 heat-map pixel) at the projections of pts (B, J, 3), float64 (B, V, J, H, W)."""
-    B, J, _ = pts.shape
-    x, y, _ = project(pts.double().view(B, 1, J, 1, 3), rec, None if ctm is None else ctm.double(), H, W)
-    xs, ys = torch.arange(W, dtype=torch.float64).view(1, 1, 1, 1, W), torch.arange(H, dtype=torch.float64).view(1, 1, 1, H, 1)
-    return height * torch.exp(-((xs - x.unsqueeze(-1)) ** 2 + (ys - y.unsqueeze(-1)) ** 2) / 2.0)
 
 
 # --------------------------------------------------------------------------- data, computed once and shared (never modified)
@@ -217,23 +84,9 @@ def shape_data(shape):
     return _CACHE[shape]
 
 
-def ulp32(m):
-    return 0.0 if m == 0.0 else 2.0 ** (math.floor(math.log2(m)) - 23)
-
-
 def own_deviation(d, name):
     """The fp32 statement's deviation from the float64 statement for one output kind: the maximum over the cases of the shape."""
     return max(float((ref["f32"][name].double() - ref["f64"][name]).abs().max()) for *_, ref in d["cases"].values())
-
-
-def yardstick(what, got, f32, f64, shape_own):
-    """(HIP deviation, allowed deviation) of one output against the float64 statement; prints the figures of this case."""
-    f64 = f64.double()
-    err, own = float((got.double().cpu() - f64).abs().max()), float((f32.double() - f64).abs().max())
-    floor = 4.0 * ulp32(float(f64.abs().max()))
-    print(f"    {what}: |hip - f64| {err:.3e}, |torch fp32 - f64| {own:.3e} (largest of the shape's cases {shape_own:.3e}), "
-          f"ratio {err / own if own else float('inf'):.3g}, 4 ulp floor {floor:.3e}, largest entry {float(f64.abs().max()):.4g}")
-    return err, max(MARGIN * shape_own, floor)
 
 
 def launch(d, hm, conf, centers, G, beta, thr, cube=CUBE, center_ok=None):
@@ -364,7 +217,7 @@ def test_a_voxel_on_the_optical_axis():
     o = offsets(G, cube, torch.float64)
     on_axis = ((centers[0, 0].double() + o)[:, :2] == torch.tensor([-6.0, 0.0], dtype=torch.float64)).all(-1)
     assert int(on_axis.sum()) == G                                                 # the whole column, exactly
-    x, y, take = project(centers.double().view(1, 1, 2, 1, 3) + o, rec, None, 64, 64)
+    x, y, take = heatmap_coords(centers.double().view(1, 1, 2, 1, 3) + o, rec, None, 64, 64)
     # z = -12, -8, -4, 0 of view 0 give no sample; column (6, 3) is camera_front_right's axis (x = 6) and does the same in view 1
     assert int((~take[0, 0, 0]).sum()) == 4 and int((~take[0, 1, 0]).sum()) == 4 and not bool((~take[0, 2:]).any())
     assert int((~take[0, :, 1]).sum()) == 0                                        # the second cube is wholly in front
@@ -424,8 +277,8 @@ def test_the_fusion_picks_the_point_all_views_agree_on():
     hm = maps.float().contiguous()
     conf = torch.ones(1, 4, J)
     centers = ((P + Q) / 2).float()
-    xq, yq, _ = project(Q.view(1, 1, J, 1, 3), rec, None, 64, 64)
-    xp, yp, _ = project(P.view(1, 1, J, 1, 3), rec, None, 64, 64)
+    xq, yq, _ = heatmap_coords(Q.view(1, 1, J, 1, 3), rec, None, 64, 64)
+    xp, yp, _ = heatmap_coords(P.view(1, 1, J, 1, 3), rec, None, 64, 64)
     hard = hm[0, 0].view(J, -1).argmax(-1)
     hx, hy = (hard % 64).double(), (hard // 64).double()
     to_q = torch.hypot(hx - xq[0, 0, :, 0], hy - yq[0, 0, :, 0])

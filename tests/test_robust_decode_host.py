@@ -8,8 +8,8 @@ import ctypes
 import pytest
 import torch
 
+import fisheye_statement as FS
 import robust_statement as RS
-import test_gpu_triangulate as TT
 
 
 def _meta_cams(V=4):
@@ -36,7 +36,7 @@ def test_operators_are_registered_with_fake_implementations_and_no_gradient():
 
 def test_public_functions_give_the_documented_shapes_on_meta():
     from egorear_amd import decode
-    cams = TT.rig()
+    cams = FS.rig()
     for B, V, J, K, rw in ((2, 4, 15, 3, False), (1, 2, 3, 1, False), (3, 3, 2, 4, False), (2, 4, 5, 4, True), (1, 2, 1, 1, True)):
         hm = torch.empty(B, V, J, 64, 64, device="meta")
         ctm = torch.empty(B, V, 4, 4, device="meta") if rw else None
@@ -60,7 +60,7 @@ def test_decode_joints_3d_robust_traces_as_one_graph_of_three_launches():
     import torch._dynamo as dynamo
     from egorear_amd import decode
     lin = torch.nn.Conv2d(4, 15, 1, device="meta")
-    cams = TT.rig()
+    cams = FS.rig()
 
     def serving_side(feat):
         hm = lin(feat).view(2, 4, 15, 64, 64)
@@ -81,7 +81,7 @@ def test_decode_joints_3d_robust_traces_as_one_graph_of_three_launches():
 
 def test_bad_parameters_are_refused_before_any_launch():
     from egorear_amd import decode, hip
-    cams = TT.rig()
+    cams = FS.rig()
     hm = torch.zeros(1, 4, 2, 16, 16, device="meta")
     for kw in ({"k": 0}, {"k": 5}, {"k": 2.0}, {"nms_radius": 0}, {"nms_radius": 4}, {"refine_radius": -1}, {"refine_radius": 4},
                {"beta": 0.0}, {"beta": float("inf")}, {"threshold": float("nan")}):
@@ -129,7 +129,7 @@ def test_bad_parameters_are_refused_before_any_launch():
 
 def test_cpu_tensors_are_refused():
     from egorear_amd import decode, hip
-    cams = TT.rig()
+    cams = FS.rig()
     hm = torch.zeros(1, 4, 2, 16, 16)
     with pytest.raises(ValueError, match="no CPU path"):
         decode.find_peaks_2d(hm)
@@ -188,11 +188,11 @@ def test_statement_known_answers_of_the_peaks():
 def _projected_candidates(V, K, g, rw=False):
     """Exact projections of random points as candidate 0 of every view, a higher-scored distractor in view 1 (slot order: best first)."""
     B, J = 2, 5
-    cams = TT.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
-    rec = TT.records(cams)
-    ctm = TT.random_ctm(B, V, cams, g) if rw else None
-    pts = TT.random_points(B, J, g)
-    true = TT.project(pts, rec, ctm) * RS.HM
+    cams = FS.rig("ego4view_rw" if rw else "ego4view_syn")[:V]
+    rec = FS.records(cams)
+    ctm = FS.random_ctm(B, V, cams, g) if rw else None
+    pts = FS.random_points(B, J, g)
+    true = FS.project(pts, rec, ctm) * RS.HM
     cand = torch.zeros(B, V, J, K, 2, dtype=torch.float64)
     cscore = torch.zeros(B, V, J, K, dtype=torch.float64)
     cindex = torch.full((B, V, J, K), -1, dtype=torch.int64)
@@ -215,7 +215,7 @@ def test_statement_chooses_the_candidates_the_views_agree_on(V, K, rw):
     assert torch.equal(ref["choice"], want) and bool((ref["inliers"] == V).all()) and bool((ref["hyp"] >= 0).all())
     assert torch.equal(ref["sel_coords"], RS.gather_choice(cand, cscore, want)[0]) and bool((ref["sel_conf"] == 0.9).all())
     assert float((ref["score"] - 0.9 * V).abs().max()) < 1e-9
-    pose, _, _, ok = TT.statement(ref["sel_coords"], ref["sel_conf"], rec, ctm, 1.0 / RS.HM, 1.0 / RS.HM)
+    pose, _, _, ok = FS.statement(ref["sel_coords"], ref["sel_conf"], rec, ctm, 1.0 / RS.HM, 1.0 / RS.HM)
     err = float((pose - pts).norm(dim=-1).max())
     print(f"V {V} K {K} rw {rw}: pose error {err:.3e} cm, decided {int(RS.decided(ref).sum())} of {ref['hyp'].numel()}")
     assert bool(ok.all()) and err < 1e-3
@@ -228,7 +228,7 @@ def test_statement_reports_no_consensus_for_inconsistent_candidates():
     rec, _, pts, cand, cscore, cindex = _projected_candidates(4, 2, g)
     # every view looks at a different point: no two rays meet within 2 px of a third view's candidate, and min_views = 3 asks for one
     for v in range(4):
-        cand[:, v, :, 0] = (TT.project(TT.random_points(2, 5, g), rec, None) * RS.HM)[:, v]
+        cand[:, v, :, 0] = (FS.project(FS.random_points(2, 5, g), rec, None) * RS.HM)[:, v]
     cindex[..., 1] = -1                                                               # and the second slots are empty
     ref = RS.consensus_statement(cand, cscore, cindex, rec, None, 1.0 / RS.HM, 1.0 / RS.HM, 2.0, 3)
     assert bool((ref["hyp"] == -1).all()) and bool((ref["choice"] == -1).all()) and bool((ref["inliers"] == 0).all())

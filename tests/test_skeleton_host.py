@@ -8,8 +8,8 @@ import ctypes
 import pytest
 import torch
 
+import fisheye_statement as FS
 import skeleton_statement as SS
-import test_gpu_triangulate as TT
 
 # (B, V, J, rw)
 META_SHAPES = ((2, 4, 15, False), (1, 2, 5, False), (3, 3, 2, False), (2, 4, 16, True), (1, 4, 1, False))
@@ -52,7 +52,7 @@ def test_operators_are_registered_with_fake_implementations_and_no_gradient():
 
 def test_public_functions_give_the_documented_shapes_on_meta():
     from egorear_amd import decode
-    cams = TT.rig()
+    cams = FS.rig()
     for B, V, J, rw in META_SHAPES:
         a = _meta(B, V, J, rw)
         parents = None if J in (15, 16) else SS.default_parents(J)
@@ -81,7 +81,7 @@ def test_decode_joints_3d_skeleton_traces_as_one_graph_of_three_launches():
     import torch._dynamo as dynamo
     from egorear_amd import decode
     lin = torch.nn.Conv2d(4, 15, 1, device="meta")
-    cams = TT.rig()
+    cams = FS.rig()
     L = torch.empty(15, device="meta")
 
     def serving_side(feat, prev, prev_ok):
@@ -103,7 +103,7 @@ def test_decode_joints_3d_skeleton_traces_as_one_graph_of_three_launches():
 
 def test_bad_tables_and_parameters_are_refused_before_any_launch():
     from egorear_amd import decode, hip
-    cams = TT.rig()
+    cams = FS.rig()
     a = _meta(2, 4, 5, False)
     good = [0, 0, 1, 1, 3]
     _fit_op(decode, a, good)
@@ -167,7 +167,7 @@ def test_bad_tables_and_parameters_are_refused_before_any_launch():
 
 def test_cpu_tensors_are_refused():
     from egorear_amd import decode, hip
-    cams = TT.rig()
+    cams = FS.rig()
     good = [0, 0, 1]
     coords, conf, L, init, ok = torch.zeros(1, 4, 3, 2), torch.ones(1, 4, 3), torch.ones(3), torch.zeros(1, 3, 3), torch.ones(1, 3, dtype=torch.uint8)
     with pytest.raises(ValueError, match="no CPU path"):
@@ -246,7 +246,7 @@ def test_without_bones_and_prior_the_fit_is_the_triangulation(B, V, J, rw):
     conf[B - 1, :, 1] = 0.3                      # another has no view
     pr = _problem(sc, 0.0, conf=conf)
     out, E0, grad, steps = SS.fit_statement(pr, 16)
-    pts, cost, _, ok = TT.statement(sc["coords"].double(), conf.double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
+    pts, cost, _, ok = FS.statement(sc["coords"].double(), conf.double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)
     assert int((~ok).sum()) == 2
     # (the bone of the one-view joint is constrained and its parent active, so it takes part; lambda = 0 leaves it on its ray)
     assert bool(out["valid"][ok].all()) and not bool(out["valid"][B - 1, 1])
@@ -259,7 +259,7 @@ def test_without_bones_and_prior_the_fit_is_the_triangulation(B, V, J, rw):
 @pytest.mark.parametrize("B,V,J,rw,chain", [(2, 4, 15, False, False), (2, 4, 16, True, False), (2, 2, 5, False, True)])
 def test_noise_free_projections_and_true_lengths_return_the_true_pose(B, V, J, rw, chain):
     sc = SS.scene(B, V, J, rw, chain, noise=0.0)
-    exact = TT.project(sc["pts"], sc["rec"], sc["ctm"]) * SS.HM                       # float64: not rounded to fp32
+    exact = FS.project(sc["pts"], sc["rec"], sc["ctm"]) * SS.HM                       # float64: not rounded to fp32
     sc["lengths"] = (sc["pts"] - sc["pts"][:, list(sc["parents"])]).norm(dim=-1)[0]
     for lam, rho in ((1.0, 0.0), (10.0, 0.0), (1.0, 1e-3)):
         pr = _problem(sc, lam, rho, coords=exact)
@@ -275,7 +275,7 @@ def test_noise_free_projections_and_true_lengths_return_the_true_pose(B, V, J, r
     # twice, and both points have energy 0: from 3 cm off the fit lands on one of them, from 0.5 cm off on the true one.)
     leaf = SS.limb_joint(sc["parents"])
     conf = SS.keep_views(sc, leaf, 1)
-    ok = TT.statement(exact, conf.double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)[3]
+    ok = FS.statement(exact, conf.double(), sc["rec"], sc["ctm"], 1.0 / SS.HM, 1.0 / SS.HM)[3]
     assert not bool(ok[:, leaf].any()) and int((~ok).sum()) == B
     out = SS.fit_statement(_problem(sc, 1.0, conf=conf, coords=exact), 48)[0]
     assert bool(out["valid"].all()) and float(out["energy"].max()) < 1e-12

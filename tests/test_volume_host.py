@@ -2,20 +2,10 @@
 autograd formula that reaches the heat maps only, both public functions give the documented shapes on meta tensors,
 `decode_joints_3d_volumetric` traces under Dynamo as one graph, every limit of the kernels is refused before any launch, and CPU
 tensors are refused."""
-import os
-
 import pytest
 import torch
 
-NAMES = ("camera_front_left", "camera_front_right", "camera_back_left", "camera_back_right")
-
-
-def _rig(model="ego4view_syn"):
-    import egorear_amd
-    from egorear_amd.camera import FishEyeCameraCalibratedModel
-    calib = os.path.join(os.path.dirname(os.path.abspath(egorear_amd.__file__)), "calib", "ego4view")
-    return [FishEyeCameraCalibratedModel(model, calib, n) for n in NAMES]
-
+from fisheye_statement import rig
 
 def _meta(*shape, **kw):
     return torch.empty(*shape, device="meta", **kw)
@@ -50,7 +40,7 @@ def test_operators_are_registered_with_fake_implementations():
 
 def test_public_functions_give_the_documented_shapes_on_meta():
     from egorear_amd import decode
-    cams = _rig()
+    cams = rig()
     hm = _meta(2, 4, 15, 64, 64)
     out = decode.fuse_joints_volumetric(hm, _meta(2, 15, 3), cams)
     assert isinstance(out, decode.Volume3D) and out._fields == ("pose", "peak", "index", "spread", "valid")
@@ -73,7 +63,7 @@ def test_decode_joints_3d_volumetric_traces_as_one_graph():
     import torch._dynamo as dynamo
     from egorear_amd import decode
     lin = torch.nn.Conv2d(4, 15, 1, device="meta")
-    cams = _rig()
+    cams = rig()
 
     def serving_side(feat):
         hm = lin(feat).view(2, 4, 15, 64, 64)
@@ -95,7 +85,7 @@ def test_decode_joints_3d_volumetric_traces_as_one_graph():
 def test_the_gradient_of_the_chain_reaches_the_heat_maps_on_meta():
     from egorear_amd import decode
     hm = _meta(2, 4, 15, 64, 64, requires_grad=True)
-    vol, tri, _ = decode.decode_joints_3d_volumetric(hm, _rig())
+    vol, tri, _ = decode.decode_joints_3d_volumetric(hm, rig())
     assert vol.pose.requires_grad and vol.peak.requires_grad and not vol.spread.requires_grad
     (g,) = torch.autograd.grad([vol.pose, vol.peak], [hm], [torch.empty_like(vol.pose), torch.empty_like(vol.peak)])
     assert g.shape == hm.shape
@@ -103,7 +93,7 @@ def test_the_gradient_of_the_chain_reaches_the_heat_maps_on_meta():
 
 def test_bad_operands_are_refused_before_any_launch():
     from egorear_amd import decode, hip
-    cams = _rig()
+    cams = rig()
     rec = torch.zeros(4, 30)
     hm, conf, centers = torch.zeros(2, 4, 3, 64, 64), torch.ones(2, 4, 3), torch.zeros(2, 3, 3)
 
@@ -183,7 +173,7 @@ def test_bad_operands_are_refused_before_any_launch():
 
 def test_cpu_tensors_are_refused():
     from egorear_amd import decode, hip
-    cams = _rig()
+    cams = rig()
     hm, conf, centers, rec = torch.zeros(2, 4, 3, 16, 16), torch.ones(2, 4, 3), torch.zeros(2, 3, 3), torch.zeros(4, 30)
     with pytest.raises(RuntimeError, match="no CPU path"):
         decode.fuse_joints_volumetric(hm, centers, cams)
