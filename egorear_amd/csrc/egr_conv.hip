@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "egr_conv_shared.h"
+#include "egr_up2.h"
 
 using namespace egrc;
 
@@ -1673,11 +1674,23 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_tap2_kernel(const ConvArgs 
 // per pixel; the weight image (pack_w6 order: k = 8h + j) is permuted to match while it is copied into LDS.
 // RESK: 0 no residual, 1 residual of the output's shape (before / behind the activation: run time), 2 half-resolution residual
 // up-sampled on the fly (EGR_RES_UP2_BEFORE_ACT); the ReLU is a run-time clamp bound.
-template <int KS, int NCF, int RESK, int NPL = 3>
-__global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
+// INK (input kind): 0 = x is the operand; 1 = x is the HALF-RESOLUTION tensor and the operand is ReLU(bilinear x2(x)), align_corners=True
+// (egr_conv_aux.in_mode = EGR_IN_UP2_RELU, arithmetic of egr_up2.h: bit-identical to upsample2x_kernel(relu = 1) followed by INK 0);
+// 2 = the same, and the launch also writes the operand out (egr_conv_aux.in_up2_out) for the consumers that read it from memory.
+// A wave's 32 output pixels lie in one output row (wo % 32 == 0): they need 2 source rows x at most 18 source pixels.  Per pair of k steps
+// (128 bytes of a pixel row) those 36 x 128 bytes are fetched ONCE per wave - 4.5 loads per lane, one tile ahead like the plain form's -
+// and go through the wave's LDS patch, from which every lane reads the four corners of its own pixel (no barrier: wave-private).
+template <int KS, int NCF, int RESK, int INK, int NPL>
+__device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
+    constexpr bool UP2 = INK != 0;
+    static_assert(!UP2 || (RESK == 0 && NPL == 2 && KS % 2 == 0), "up-sample-on-load: plain fp16-scheme launches");
+    constexpr int UPW = 18, UPQ = 2 * UPW * 8, UPL = (UPQ + 63) / 64;      // source pixels per row; 16-byte pieces per k-step pair; loads per lane
     constexpr int WBYTES = NCF * KS * NPL * 1024;
     constexpr int NPR = split_npr(NPL);
-    constexpr int PATCH = 32 * 144;        // per-wave epilogue patch: 32 pixels x 32 channels, rows padded to 144 bytes
+    // per-wave patch, rows padded to 144 bytes: 32 pixels x 32 channels (epilogue) / 36 source pixels x 32 channels, and behind them
+    // (INK 2) the 32 x 32 patch through which the operand written out turns row-major
+    constexpr int OPATCH = 2 * UPW * 144;
+    constexpr int PATCH = UP2 ? OPATCH + (INK == 2 ? 32 * 144 : 0) : 32 * 144;
     __shared__ __attribute__((aligned(16))) uint8_t lds[WBYTES + NCF * 32 * 8 + 8 * PATCH];
     float* const s_sc = reinterpret_cast<float*>(lds + WBYTES);
     float* const s_sh = s_sc + NCF * 32;
@@ -1718,9 +1731,31 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
         }
         return (tile < T && m < a.M) ? (xb + ipix * d.ldx) * 4 + h * 16 : OOB;
     };
+    // INK != 0: byte offsets of the lane's UPL pieces of a tile's source pixels (piece e = lane + 64 i: source pixel e / 8 = row e / 144,
+    // column e / 8 % 18 of the tile's window, 16-byte piece e % 8 of the k-step pair's 128 bytes); columns past the image repeat the last one
+    const int hs = d.h >> 1, ws = d.w >> 1;
+    const float up_sh = UP2 ? egr_up2::scale(hs, d.h) : 0.f, up_sw = UP2 ? egr_up2::scale(ws, d.w) : 0.f;
+    auto up_src_off = [&](int tile, int (&so)[UPL]) {
+        const int m0 = tile * 32;
+        int n, pix;
+        if (a.howo_shift >= 0) { n = m0 >> a.howo_shift; pix = m0 & (HoWo - 1); }
+        else { n = fdiv(m0, a.dHoWo); pix = m0 - n * HoWo; }
+        const int oy = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), ox0 = pix - oy * d.wo;
+        const egr_up2::Axis ay = egr_up2::axis(up_sh, oy, hs);
+        const int sx0 = egr_up2::first_index(up_sw, ox0);
+        const int xb = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+#pragma unroll
+        for (int i = 0; i < UPL; ++i) {
+            const int e = lane + 64 * i, s = e >> 3, r = s >= UPW ? 1 : 0, c = s - UPW * r;
+            const int col = min(sx0 + c, ws - 1), row = r ? ay.i1 : ay.i0;
+            so[i] = (tile < T && e < UPQ) ? (xb + (row * ws + col) * d.ldx) * 4 + (e & 7) * 16 : OOB;
+        }
+    };
+    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(
+        uniform_ptr(INK == 2 ? a.up2_out + (int64_t)grp * a.M * d.cin : a.y), 0, 0x80000000u, 0x00020000);
     // weights -> LDS: 16-byte loads of the image (lane (p, q) of a fragment = k 8q .. 8q+7), each written as two 8-byte pieces:
     // its half hh goes to the new lane (p, hh), position q  (new lane (p, h): k {4h .. 4h+3} u {8+4h .. 8+4h+3})
-    u32x4 raw[2 * KS];
+    u32x4 raw[UP2 ? (KS / 2) * UPL : 2 * KS];
     {
         const uint8_t* const wimg = reinterpret_cast<const uint8_t*>(a.w) + (int64_t)grp * d.gw * 2;
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -1733,9 +1768,18 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
             const int cf = v / (KS * 64 * NPL), rem = v - cf * (KS * 64 * NPL);
             wv[i] = *reinterpret_cast<const u32x4*>(wimg + ((int64_t)(tn * NCF + cf) * a.ktiles * 2 * NPL) * 1024 + rem * 16);
         }
-        const int xo = x_off(t);
+        if constexpr (UP2) {
+            int so[UPL];
+            up_src_off(t, so);
 #pragma unroll
-        for (int i = 0; i < 2 * KS; ++i) raw[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo + i * 32, 0, 0);
+            for (int kp = 0; kp < KS / 2; ++kp)
+#pragma unroll
+                for (int i = 0; i < UPL; ++i) raw[kp * UPL + i] = __builtin_amdgcn_raw_buffer_load_b128(rx, so[i] + kp * 128, 0, 0);
+        } else {
+            const int xo = x_off(t);
+#pragma unroll
+            for (int i = 0; i < 2 * KS; ++i) raw[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo + i * 32, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = tid + 512 * i;
@@ -1760,8 +1804,30 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
 #ifdef PW_EXP_NOLOAD
             const int xo_n = OOB;
 #else
-            const int xo_n = x_off(t + NW);
+            const int xo_n = UP2 ? OOB : x_off(t + NW);
 #endif
+            // INK != 0: the next tile's source pieces; this lane's pixel - its four corners in the patch, their weights, its place in the
+            // operand written out
+            int so_n[UPL], o00 = 0, o01 = 0, o10 = 0, o11 = 0, uo = OOB;
+            float ux0 = 0.f, ux1 = 0.f, uy0 = 0.f, uy1 = 0.f;
+            uint8_t* const upatch = lds + WBYTES + NCF * 32 * 8 + wave * PATCH;
+            if constexpr (UP2) {
+                up_src_off(t + NW, so_n);
+                const int m = t * 32 + p;
+                int n, pix;
+                if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
+                else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
+                const int oy = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), ox = pix - oy * d.wo;
+                const egr_up2::Axis ay = egr_up2::axis(up_sh, oy, hs), ax = egr_up2::axis(up_sw, ox, ws);
+                const int sx0 = egr_up2::first_index(up_sw, ox - p);        // (the tile starts at column ox - p of the same row)
+                uy0 = ay.l0; uy1 = ay.l1; ux0 = ax.l0; ux1 = ax.l1;
+                o00 = (ax.i0 - sx0) * 144 + h * 16;
+                o01 = (ax.i1 - sx0) * 144 + h * 16;
+                o10 = o00 + UPW * 144;
+                o11 = o01 + UPW * 144;
+                // (written out like the epilogue's rows: lane = (row i * 8 + lane / 8, 16-byte piece lane % 8) of the pair's 128 bytes)
+                if (INK == 2) uo = ((t * 32 + (lane >> 3)) * d.cin + (lane & 7) * 4) * 4;
+            }
             f32x16 acc[NCF];
 #pragma unroll
             for (int cf = 0; cf < NCF; ++cf)
@@ -1771,10 +1837,56 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
             for (int ks = 0; ks < KS; ++ks) {
                 // split the lane's 8 values of this k step (hi + mid + lo, exact  /  h + l of the pre-scaled value)
                 unsigned xh[4], xm[4], xl[4];
+                if constexpr (UP2) {
+                    if ((ks & 1) == 0) {
+                        // this pair's source pieces -> the patch (a wave's LDS operations execute in order: the previous pair's corner
+                        // reads and the previous tile's epilogue are done with it), then the same pair of the wave's next tile is requested
+                        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const u32x4& src = raw[2 * ks + (e >> 1)];
-                    split_pair<NPL>(__uint_as_float(src[2 * (e & 1)]), __uint_as_float(src[2 * (e & 1) + 1]), sa, xh[e], xm[e], xl[e]);
+                        for (int i = 0; i < UPL; ++i) {
+                            const int e = lane + 64 * i;
+                            if (e < UPQ) *reinterpret_cast<u32x4*>(upatch + (e >> 3) * 144 + (e & 7) * 16) = raw[(ks >> 1) * UPL + i];
+                        }
+                        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                        for (int i = 0; i < UPL; ++i)
+                            raw[(ks >> 1) * UPL + i] = __builtin_amdgcn_raw_buffer_load_b128(rx, so_n[i] + (ks >> 1) * 128, 0, 0);
+                    }
+                    float xv[8];
+#pragma unroll
+                    for (int e2 = 0; e2 < 2; ++e2) {
+                        const int ko = (ks & 1) * 64 + e2 * 32;
+                        const f32x4 v00 = *reinterpret_cast<const f32x4*>(upatch + o00 + ko), v01 = *reinterpret_cast<const f32x4*>(upatch + o01 + ko);
+                        const f32x4 v10 = *reinterpret_cast<const f32x4*>(upatch + o10 + ko), v11 = *reinterpret_cast<const f32x4*>(upatch + o11 + ko);
+                        f32x4 u;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) u[c] = egr_up2::lerp_relu(v00[c], v01[c], v10[c], v11[c], ux0, ux1, uy0, uy1);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) xv[e2 * 4 + c] = u[c];
+                        if constexpr (INK == 2) *reinterpret_cast<f32x4*>(upatch + OPATCH + p * 144 + ko + h * 16) = u;
+                    }
+                    if constexpr (INK == 2) {
+                        if (ks & 1) {
+                            // the pair's 128 bytes of the wave's 32 pixels, out as whole lines: an instruction writes 8 rows x 128 bytes
+                            // (stored from the lanes that computed them it wrote 32-byte pieces of 32 rows: 2.7 TB/s for the launch).
+                            // Far beyond the last-level cache: non-temporal, as upsample2x_kernel writes the same tensor.
+                            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const u32x4 v = *reinterpret_cast<const u32x4*>(upatch + OPATCH + (i * 8 + (lane >> 3)) * 144 + (lane & 7) * 16);
+                                __builtin_amdgcn_raw_buffer_store_b128(v, ru, uo + i * 8 * d.cin * 4 + (ks >> 1) * 128, 0, 2);
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) split_pair<NPL>(xv[2 * e], xv[2 * e + 1], sa, xh[e], xm[e], xl[e]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const u32x4& src = raw[2 * ks + (e >> 1)];
+                        split_pair<NPL>(__uint_as_float(src[2 * (e & 1)]), __uint_as_float(src[2 * (e & 1) + 1]), sa, xh[e], xm[e], xl[e]);
+                    }
                 }
                 u32x4 xb[NPL];
                 xb[0] = u32x4{xh[0], xh[1], xh[2], xh[3]};
@@ -1783,10 +1895,12 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
                 // the registers of a k-step pair (one 128-byte line of the pixel's row) are free: request the same pair of the wave's
                 // next tile - four loads back to back, so the line is fetched once
 #ifndef PW_EXP_LOAD2
-                if (ks & 1) {
+                if constexpr (!UP2) {
+                    if (ks & 1) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        raw[2 * ks - 2 + i] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo_n + (ks - 1) * 64 + i * 32, 0, 0);
+                        for (int i = 0; i < 4; ++i)
+                            raw[2 * ks - 2 + i] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo_n + (ks - 1) * 64 + i * 32, 0, 0);
+                    }
                 }
 #else
                 raw[2 * ks] = __builtin_amdgcn_raw_buffer_load_b128(rx, xo_n + ks * 64, 0, 0);
@@ -1915,6 +2029,23 @@ __global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
         }
     }
     if (a.amax_out) amax_flush(a.amax_out, amx, (int)blockIdx.x * 8 + wave);
+}
+
+template <int KS, int NCF, int RESK, int NPL = 3>
+__global__ __launch_bounds__(512) void conv_pw_x6_kernel(const ConvArgs a) {
+    conv_pw_x6_body<KS, NCF, RESK, 0, NPL>(a);
+}
+
+// The up-sample-on-load forms (INK 1 / 2).  Their launch arguments are ConvArgs in a type of their own, like the one-product
+// role-split kernels': the kernels that take a bare ConvArgs are the set tools/conv_plan_cases.py lists by that signature and
+// tests/test_conv_plan.py holds to its table - no launch without egr_conv_aux.in_mode reaches these (tests/test_up2_on_load_host.py
+// covers their plans).
+struct ConvArgsUp2 {
+    ConvArgs a;
+};
+template <int KS, int NCF, int INK, int NPL>
+__global__ __launch_bounds__(512) void conv_pw_x6_up2_kernel(const ConvArgsUp2 u) {
+    conv_pw_x6_body<KS, NCF, 0, INK, NPL>(u.a);
 }
 
 // persistent variant (short K: a tile is mostly fixed cost and HBM traffic - the next tile's decode and first loads overlap the
@@ -2266,6 +2397,16 @@ int conv_check(const egr_conv_desc& d, const ConvOperands& o) {
          d.act == EGR_ACT_GELU))
         return EGR_EINVAL;
     if (bnst && !vec_ok) return EGR_EINVAL;
+    // the operand up-sampled as it is loaded (egr_conv_aux.in_mode): what the streaming kernel's input variant covers, nothing else
+    if (aux && aux->in_mode != EGR_IN_PLAIN) {
+        if (aux->in_mode != EGR_IN_UP2_RELU) return EGR_EINVAL;
+        if (fmt != EGR_W_F16X2 || d.kh != 1 || d.kw != 1 || d.stride != 1 || d.pad != 0 || d.transposed || d.out_nchw || o.mask || bnst ||
+            d.res_mode != EGR_RES_NONE || o.rowscale || o.rowmask || d.split_k > 1 || d.h != d.ho || d.w != d.wo || (d.h & 1) || (d.w & 1) ||
+            d.w % 32 != 0 || d.cin != 128 || !vec_ok || d.cout % 4 != 0 || d.act == EGR_ACT_GELU)
+            return EGR_EINVAL;
+        // the operand written out: dense, 32-bit byte offsets inside a group
+        if (aux->in_up2_out && ((((uintptr_t)aux->in_up2_out) & 15) || (int64_t)d.n * d.h * d.w * d.cin * 4 >= (1LL << 31))) return EGR_EINVAL;
+    } else if (aux && aux->in_up2_out) return EGR_EINVAL;
     if (o.mask &&   // masked data gradient: plain 16-byte epilogue only
         (!vec_ok || d.cout % 4 != 0 || o.scale || o.shift || o.rowscale || o.rowmask || d.act != EGR_ACT_NONE || d.out_nchw ||
          d.res_mode == EGR_RES_AFTER_ACT || ((uintptr_t)o.mask & 15)))
@@ -2289,6 +2430,8 @@ void conv_geometry(ConvArgs& a, const egr_conv_desc& dd, const ConvOperands& o, 
     a.bn_part = bnst ? o.aux->bn_partials : nullptr;
     a.bn_tiles_host = bnst ? o.aux->bn_tiles_out : nullptr;
     a.bn_cap = bnst ? (size_t)o.aux->bn_capacity : 0;
+    a.in_mode = o.aux ? o.aux->in_mode : EGR_IN_PLAIN;
+    a.up2_out = o.aux ? o.aux->in_up2_out : nullptr;
     a.cnt = nullptr;
     a.dbg = dbg;
     a.M = d.n * d.ho * d.wo;
@@ -2389,9 +2532,11 @@ bool plan_stream(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out)
           d.act != EGR_ACT_GELU && (d.cin == 64 || d.cin == 128) && a.Npad % 64 == 0 && (d.stride == 2 || (d.h == d.ho && d.w == d.wo)) &&
           (int64_t)a.M * d.groups >= k.pw_min_rows && p.yspan * 4 < (1LL << 31) && (!d.res_mode || p.rspan * 4 < (1LL << 31))))
         return false;
+    if (a.in_mode != EGR_IN_PLAIN && !(p.h2 && a.M % 32 == 0)) return false;     // (conv_check has held the rest of the mode's rules)
     const int ncf = (a.Npad % 128 == 0) ? 4 : 2;
     const int resk = d.res_mode == EGR_RES_NONE ? 0 : (d.res_mode == EGR_RES_UP2_BEFORE_ACT ? 2 : 1);
-    egr_conv_plan_t pl = plan_tile(p, EGR_ROUTE_STREAM_1X1, 32, ncf * 32, 100 * (d.cin / 16) + 10 * ncf + resk, 512);
+    const int ink = a.in_mode == EGR_IN_PLAIN ? 0 : (a.up2_out ? 2 : 1);
+    egr_conv_plan_t pl = plan_tile(p, EGR_ROUTE_STREAM_1X1, 32, ncf * 32, 1000 * ink + 100 * (d.cin / 16) + 10 * ncf + resk, 512);
     // `pw_blocks` resident workgroups, each walking 32-row steps eight at a time (one per wave) down its column of tiles
     int nblk = k.pw_blocks / (pl.tiles_n * d.groups);
     if (nblk < 1) nblk = 1;
@@ -2470,6 +2615,7 @@ int plan_tiled(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
 }
 
 int conv_plan(const ConvProblem& p, const ConvKnobs& k, egr_conv_plan_t& out) {
+    if (p.a.in_mode != EGR_IN_PLAIN) return plan_stream(p, k, out) ? 0 : EGR_EINVAL;    // (the one route with that input variant)
     if (!(plan_small(p, k, out) || plan_tapx(p, k, out) || plan_tap(p, k, out) || plan_tap2(p, k, out) || plan_stream(p, k, out)))
         if (const int rc = plan_tiled(p, k, out)) return rc;
     // the statistics slabs (one per M tile of the height just chosen) must fit the caller's buffer
@@ -2503,6 +2649,10 @@ bool go_tiled(const egr_conv_plan_t& pl, Go go) {
 int launch_conv(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t s) {
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z), dim3((unsigned)pl.block), 0, s, a);
+        return true;
+    };
+    auto go_up2 = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z), dim3((unsigned)pl.block), 0, s, ConvArgsUp2{a});
         return true;
     };
     const int tile = pl.bm * 1000 + pl.bn;
@@ -2557,6 +2707,11 @@ int launch_conv(const egr_conv_plan_t& pl, const ConvArgs& a, hipStream_t s) {
                     case 840: return go(conv_pw_x6_kernel<8, 4, 0, NPL>);
                     case 841: return go(conv_pw_x6_kernel<8, 4, 1, NPL>);
                     case 842: return go(conv_pw_x6_kernel<8, 4, 2, NPL>);
+                    // + 1000 / + 2000: the operand up-sampled as it is loaded / and written out (fp16 scheme only)
+                    case 1820: if constexpr (NPL == 2) return go_up2(conv_pw_x6_up2_kernel<8, 2, 1, NPL>); return false;
+                    case 1840: if constexpr (NPL == 2) return go_up2(conv_pw_x6_up2_kernel<8, 4, 1, NPL>); return false;
+                    case 2820: if constexpr (NPL == 2) return go_up2(conv_pw_x6_up2_kernel<8, 2, 2, NPL>); return false;
+                    case 2840: if constexpr (NPL == 2) return go_up2(conv_pw_x6_up2_kernel<8, 4, 2, NPL>); return false;
                     default: return false;
                 }
             });

@@ -744,6 +744,7 @@ extern "C" int egr_conv1x1_chain_f32(const egr_conv_desc* dd, const float* x, co
     if (d.ldx % 4 != 0 || d.ldy % 4 != 0 || (d.res_mode && d.ldr % 4 != 0)) return EGR_EINVAL;
     if (((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)chain->w2 | (uintptr_t)y | (uintptr_t)res) & 15) return EGR_EINVAL;
     if (((uintptr_t)aux->amax_in | (uintptr_t)aux->amax_out) & 3) return EGR_EINVAL;
+    if (aux->in_mode != EGR_IN_PLAIN || aux->in_up2_out) return EGR_EINVAL;      // (the chained kernels have no up-sample-on-load variant)
     if (d.xmap.n_inner <= 0 || d.ymap.n_inner <= 0 || (d.res_mode && d.rmap.n_inner <= 0)) return EGR_EINVAL;
     if (((d.xmap.stride_inner | d.xmap.stride_outer | d.ymap.stride_inner | d.ymap.stride_outer) % 4) != 0) return EGR_EINVAL;
     if (d.res_mode && ((d.rmap.stride_inner | d.rmap.stride_outer) % 4) != 0) return EGR_EINVAL;

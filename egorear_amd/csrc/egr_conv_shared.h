@@ -69,6 +69,10 @@ struct ConvArgs {
     double* bn_part;
     int* bn_tiles_host;      // HOST pointer (conv_launch): where the launch reports its M tiles per group; capacity of bn_part in doubles
     size_t bn_cap;
+    // egr_conv_aux.in_mode = EGR_IN_UP2_RELU: x is the half-resolution tensor (d.h / 2 x d.w / 2 pixels per image), the operand is
+    // ReLU(bilinear x2(x)); up2_out (optional): the launch also writes that operand, dense ((groups,) n, d.h, d.w, cin)
+    int in_mode;
+    float* up2_out;
 };
 
 constexpr int BK = 32;

@@ -379,10 +379,13 @@ def _unpadded(m: nn.Conv2d) -> bool:
 
 
 def run_stack(st: State, seqs: Sequence[nn.Sequential], x: Img, out: Optional[Img] = None,
-              last_kw: Optional[dict] = None) -> Optional[Img]:
+              last_kw: Optional[dict] = None, up2_sink=None) -> Optional[Img]:
     """Execute tree.stack()s (one per group, identical structure): Conv2d(+ReLU) fuse into one launch; Upsample /
     MaxPool2d are their own kernels (no weights: they simply run over all groups' images).  `out` / `last_kw`
-    apply to the final op."""
+    apply to the final op.
+    up2_sink(y, out): a consumer of the stack's result that can produce `out` = ReLU(up2(y)) itself while it loads y (the lifting
+    head's first conv, hip.conv2d(up2_in=True, up2_out=out)); asked when the stack ends in the chained launch + up-sampling, it
+    returns `out` - the up-sampling launch is then skipped - or None."""
     mods = [list(s) for s in seqs]
     m0 = mods[0]
     i = 0
@@ -422,7 +425,9 @@ def run_stack(st: State, seqs: Sequence[nn.Sequential], x: Img, out: Optional[Im
                     y = hip.conv1x1_chain(x, p.w, p2.w, p.cout, p2.cout, shift1=p.shift, shift2=p2.shift, act1=act,
                                           act2=ACT_NONE if up else (ACT_RELU if relu2 else ACT_NONE), groups=p.groups,
                                           out=out if (fin and not up) else None, amax_out=st.new_amax())
-                    x = hip.upsample2x(y, out=out if fin else None, relu=True) if up else y
+                    x = up2_sink(y, out) if (up and fin and up2_sink is not None and out is not None) else None
+                    if x is None:
+                        x = hip.upsample2x(y, out=out if fin else None, relu=True) if up else y
                     i = end
                     continue
             kw = dict(last_kw or {}) if last else {}
@@ -804,8 +809,9 @@ CAPTURE = None
 
 
 def _run_refiners(st: State, rs, B: int, V: int, hm_init: torch.Tensor, feat_all: torch.Tensor, s32_all: torch.Tensor,
-                  anchors, valid, feat_ref: torch.Tensor, hm_ref: torch.Tensor):
-    """The four HeatmapMVF refiners (heatmap_mvf_ex.py:652-731), refiner g = view g, as one group of G = V."""
+                  anchors, valid, feat_ref: torch.Tensor, hm_ref: torch.Tensor, up2_sink=None):
+    """The four HeatmapMVF refiners (heatmap_mvf_ex.py:652-731), refiner g = view g, as one group of G = V.
+    up2_sink: see run_stack - who writes feat_ref when the refined features' up-sampling rides on their first reader."""
     G = len(rs)
     assert G == V
     r0 = rs[0]
@@ -854,7 +860,7 @@ def _run_refiners(st: State, rs, B: int, V: int, hm_init: torch.Tensor, feat_all
     summed = conv(st, h0, P.head3, ACT_RELU, res=ff, res_mode=RES_AFTER_ACT)   # offset_pred + frame_feat
     if CAPTURE is not None:
         CAPTURE.update(query=x.view(G, B, J, C).clone(), post_norm=xn.view(G, B, J, C).clone(), head_sum=summed.t.clone())
-    run_stack(st, [r.frame_feat_refined_proj_layers[0] for r in rs], summed, out=Img(feat_ref))
+    run_stack(st, [r.frame_feat_refined_proj_layers[0] for r in rs], summed, out=Img(feat_ref), up2_sink=up2_sink)
     # --- refined heatmaps, written as (B, V, 15, 64, 64) planes; group g = view g
     plane = J * hw
     run_stack(st, [r.conv_heatmap_layers[0] for r in rs], Img(feat_ref),
@@ -874,7 +880,7 @@ def anchors_from_heatmap_api(mod, heatmap):
     return a, m, v.bool()
 
 
-def _mvfex(mod, img: torch.Tensor, heatmap_for_anchor=None):
+def _mvfex(mod, img: torch.Tensor, heatmap_for_anchor=None, up2_sink=None):
     st = _state(mod, img.device)
     st.begin_forward()
     B, V = img.shape[:2]
@@ -896,7 +902,7 @@ def _mvfex(mod, img: torch.Tensor, heatmap_for_anchor=None):
     # --- four refiners (own weights each, G = 4), every one attending to all four views
     feat_ref = torch.empty_like(feat_all)
     hm_ref = torch.empty_like(hm_init)
-    _run_refiners(st, mod.refiners(), B, V, hm_init, feat_all, s32_all, anchors, valid, feat_ref, hm_ref)
+    _run_refiners(st, mod.refiners(), B, V, hm_init, feat_all, s32_all, anchors, valid, feat_ref, hm_ref, up2_sink=up2_sink)
     if CAPTURE is not None:
         CAPTURE.update(feat_init=_vb_view(feat_all, V, B).clone(), feat_refined=_vb_view(feat_ref, V, B).clone())
     aux = {"anchors_2d": anchors, "maxvals": maxvals, "anchors_valid": valid, "argmax_idx": index}
@@ -967,8 +973,10 @@ def _pack_pose3d(p3) -> PPose:
     return P
 
 
-def _pose3d(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tensor, B: int, V: int, ctm, behind: Optional[State] = None):
+def _pose3d(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tensor, B: int, V: int, ctm, behind: Optional[State] = None,
+            first: Optional[Img] = None):
     """EgoPoseFormerPose3D.forward (egoposeformer_mvf_ex.py:422-452).  feat_*: (V*B, 64, 64, 128) view-major NHWC.
+    first: conv_frame_feat[0] (+ ReLU) of feat_final, where the caller has run it already (mvfex_forward_api: it produces feat_final).
     behind: the state of the heat-map estimator whose forward has just produced feat_* - the lifting head then goes on in ITS abs-max
     arena (one clear per forward instead of two; the records of feat_* sit in it anyway)."""
     own = st.amax
@@ -977,12 +985,12 @@ def _pose3d(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tensor, B:
     else:
         st.begin_forward()
     try:
-        return _pose3d_body(p3, st, feat_init, feat_final, B, V, ctm)
+        return _pose3d_body(p3, st, feat_init, feat_final, B, V, ctm, first)
     finally:
         st.amax = own
 
 
-def _pose3d_body(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tensor, B: int, V: int, ctm):
+def _pose3d_body(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tensor, B: int, V: int, ctm, first: Optional[Img] = None):
     P: PPose = st.get(p3, lambda: _pack_pose3d(p3))
     for t in (feat_init, feat_final):      # feature maps handed in by a caller carry no abs-max record: make one (one read each)
         if st.amax is not None and getattr(t, "_egr_amax", None) is None:
@@ -995,7 +1003,7 @@ def _pose3d_body(p3, st: State, feat_init: torch.Tensor, feat_final: torch.Tenso
     src = feat_init if p3.use_pred_heatmap_init else feat_final
     # --- proposal: conv stack on the refined features, flattened per frame, 3-layer MLP (_forward_mlp_conv)
     flat = torch.empty((B, V * 8 * 8 * 128), device=dev, dtype=torch.float32)
-    fo = run_stack(st, [p3.conv_frame_feat], Img(feat_final),
+    fo = run_stack(st, [p3.conv_frame_feat] if first is None else [p3.conv_frame_feat[2:]], Img(feat_final) if first is None else first,
                    out=Img(flat.view(B * V, 8, 8, 128)), last_kw={"ymap": NMap(B, V * 8192, 8192)})  # (v,b) -> (b,v)
     if P.mlp0_ws is not None and fo.amax is not None:
         flat._egr_amax = fo.amax
@@ -1071,9 +1079,28 @@ def mvfex_forward_api(mod, img, ctm=None):
     img = as_rgb(img)
     B, V = img.shape[:2]
     he = mod.heatmap_estimator
-    hm_init, hm_ref, feat_all, feat_ref, aux_h = _mvfex(he, img)
-    st = _state(mod.pose3d_estimator, img.device)
-    preds, aux_p = _pose3d(mod.pose3d_estimator, st, feat_all, feat_ref, B, V, ctm, behind=_state(he, img.device))
+    p3 = mod.pose3d_estimator
+    st = _state(p3, img.device)
+    # The refined features ReLU(up2(y)) have two readers: the refined heat-map head and conv_frame_feat[0] (1x1 128 -> 64 + ReLU) of
+    # the lifting head.  The latter interpolates them from the half-resolution y as it loads it and writes them out on the way
+    # (hip.conv2d up2_in / up2_out): the up-sampling launch and one read of the 537-MB tensor go.  Not under CAPTURE,
+    # not where the library refuses the launch (small batches, other arithmetic): the stack then up-samples as before.
+    m0 = p3.conv_frame_feat[0]
+    first, sink = [], None
+    if (hip.policy().up2_on_load and CAPTURE is None and len(p3.conv_frame_feat) > 2 and isinstance(m0, nn.Conv2d) and m0.kernel_size == (1, 1)
+            and m0.stride == (1, 1) and _unpadded(m0) and isinstance(p3.conv_frame_feat[1], nn.ReLU) and isinstance(p3.conv_frame_feat[2], nn.Conv2d)):
+        def sink(y: Img, out: Img) -> Optional[Img]:
+            p = st.get(m0, lambda: pack_convs([m0]))
+            if p.groups != 1 or y.c != m0.in_channels:
+                return None
+            fo = hip.conv2d(y, p.w, p.cout, 1, 1, 1, 0, scale=p.scale, shift=p.shift, act=ACT_RELU, workspace=st.workspace,
+                            amax_out=_state(he, img.device).new_amax(), up2_in=True, up2_out=out)
+            if fo is None:
+                return None
+            first.append(fo)
+            return out
+    hm_init, hm_ref, feat_all, feat_ref, aux_h = _mvfex(he, img, up2_sink=sink)
+    preds, aux_p = _pose3d(p3, st, feat_all, feat_ref, B, V, ctm, behind=_state(he, img.device), first=first[0] if first else None)
     mod.__dict__["_egr_last_aux"] = {"heatmap": aux_h, "pose3d": aux_p}
     return preds, [hm_init, hm_ref]
 

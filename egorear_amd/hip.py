@@ -74,6 +74,9 @@ class LaunchPolicy:
     layer_h2: bool = True
     fused_layer: bool = True
     fused_query: bool = True
+    # engine: the refiners' up-sampled feature map ReLU(up2(y)) is produced by the lifting head's first 1x1 conv as it loads y
+    # (egr_conv_aux.in_mode) instead of by a launch of its own; EGR_UP2_ON_LOAD=0 keeps the up-sampling launch
+    up2_on_load: bool = True
     # the half-precision TRAINING arithmetic on top of w_format "f16" (fast_training(), opt-in: outside the parity contract): the training
     # step's role-split conv launches and its split weight gradients multiply fp16-rounded operands with one product
     train_one_product: bool = False
@@ -92,7 +95,8 @@ class LaunchPolicy:
                    chain=e.get("EGR_CONV_CHAIN", "1") != "0", chain_min_rows=int(e.get("EGR_CONV_CHAIN_MIN_ROWS", "8192")),
                    chain_big=e.get("EGR_CONV_CHAIN_BIG", "1") != "0", chain_big_min_rows=int(e.get("EGR_CONV_CHAIN_BIG_MIN_ROWS", "65536")),
                    wgrad_x6=fmt != "f32", layer_h2=fp16 and e.get("EGR_LAYER_H2", "1") != "0",
-                   fused_layer=e.get("EGR_FUSED_LAYER", "1") != "0", fused_query=e.get("EGR_FUSED_QUERY", "1") != "0")
+                   fused_layer=e.get("EGR_FUSED_LAYER", "1") != "0", fused_query=e.get("EGR_FUSED_QUERY", "1") != "0",
+                   up2_on_load=e.get("EGR_UP2_ON_LOAD", "1") != "0")
 
     def replace(self, **kw) -> "LaunchPolicy":
         return dataclasses.replace(self, **kw)
@@ -211,7 +215,11 @@ class ConvDesc(C.Structure):
 class ConvAux(C.Structure):
     """egr_conv_aux of include/egorear_hip.h: side operands of the fp16 scheme (EGR_W_F16X2) and the abs-max record of the output."""
     _fields_ = [("w_descale", C.c_void_p), ("amax_in", C.c_void_p), ("amax_out", C.c_void_p),
-                ("bn_partials", C.c_void_p), ("bn_tiles_out", C.c_void_p), ("bn_capacity", C.c_int64)]
+                ("bn_partials", C.c_void_p), ("bn_tiles_out", C.c_void_p), ("bn_capacity", C.c_int64),
+                ("in_mode", C.c_int32), ("in_up2_out", C.c_void_p)]
+
+
+IN_PLAIN, IN_UP2_RELU = 0, 1      # egr_conv_aux.in_mode
 
 
 class ConvPlan(C.Structure):
@@ -681,7 +689,8 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
            split_k: int = 1, groups: int = 1, gx: Optional[int] = None, gy: Optional[int] = None,
            gr: Optional[int] = None, grs: int = 0, grm: int = 0, transposed_out_hw: Optional[tuple] = None, x6_min: Optional[tuple] = None,
            mask: Optional[Img] = None, amax_out: Optional[torch.Tensor] = None, amax_arena: Optional["AmaxArena"] = None,
-           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None, one_product: Union[bool, str, None] = None) -> Optional[Img]:
+           bn_ws: Optional[torch.Tensor] = None, bn_slabs: Optional[list] = None, one_product: Union[bool, str, None] = None,
+           up2_in: bool = False, up2_out: Optional[Img] = None) -> Optional[Img]:
     """Implicit-GEMM conv / linear.  Output goes to `out` (NHWC Img, maybe a channel slice), or to the raw
     tensor `out_nchw` (channel-major planes placed by `ymap`), or to a fresh NHWC tensor.
 
@@ -690,9 +699,18 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     image stride) unless an explicit element stride gx / gy / gr is given, in which case they describe group 0.
 
     one_product: None = the policy's forward rule (w_format "f16"), True / False = EGR_W_F16X1 on / off (tests), "train" = the training
-    step under LaunchPolicy.train_one_product: EGR_W_F16X1 | EGR_W_F16X1T, the role-split route's training launches take one product too."""
+    step under LaunchPolicy.train_one_product: EGR_W_F16X1 | EGR_W_F16X1T, the role-split route's training launches take one product too.
+
+    up2_in: x is the HALF-RESOLUTION tensor and the launch convolves ReLU(bilinear x2(x)), interpolated as it is loaded
+    (egr_conv_aux.in_mode = EGR_IN_UP2_RELU; bit-identical to upsample2x(x, relu=True) followed by the plain launch); up2_out: a dense
+    (groups * n, 2 h, 2 w, cin) Img that then also receives that operand.  Returns None - nothing launched - when the library has no
+    kernel for the call in this mode (EGR_EINVAL from egr_conv_plan): the caller materialises the up-sampled tensor instead."""
     pol = policy()
     x_full = x.t
+    if up2_in and (mask is not None or out_nchw is not None or transposed_out_hw is not None or bn_ws is not None or res_mode != RES_NONE):
+        raise RuntimeError("egorear_amd.conv2d: up2_in goes with a plain NHWC forward launch only")
+    if up2_out is not None and not up2_in:
+        raise RuntimeError("egorear_amd.conv2d: up2_out without up2_in")
     if groups > 1:
         if gx is None:
             if x.n % groups:
@@ -701,13 +719,14 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
             gx = ng * x.nstride
             x = Img(x.t[:ng], amax=x.amax)
         ng = x.n
+    ih, iw = (2 * x.h, 2 * x.w) if up2_in else (x.h, x.w)      # the image the conv runs over
     if transposed_out_hw is not None:   # data gradient: x is dy, the output is dx of the given spatial size
         ho, wo = transposed_out_hw
         if (ho + 2 * pad - kh) // stride + 1 != x.h or (wo + 2 * pad - kw) // stride + 1 != x.w:
             raise RuntimeError("egorear_amd.conv2d: transposed_out_hw inconsistent with dy's size")
     else:
-        ho = (x.h + 2 * pad - kh) // stride + 1
-        wo = (x.w + 2 * pad - kw) // stride + 1
+        ho = (ih + 2 * pad - kh) // stride + 1
+        wo = (iw + 2 * pad - kw) // stride + 1
     npad = (cout + 31) // 32 * 32
     K = kh * kw * x.c
     wshape = (groups, npad, K) if groups > 1 else (npad, K)
@@ -716,7 +735,7 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     if isinstance(w, W6) and w.f32 is not None:
         rows_all = x.n * groups * ho * wo
         # (the split kernel addresses one group's activations through a 2-GiB buffer window)
-        x_bytes = 4 * ((x.n - 1) * x.nstride + (x.h * x.w + 2 * (kh * x.w + kw + 1)) * x.ld) + 64
+        x_bytes = 4 * ((x.n - 1) * x.nstride + (ih * iw + 2 * (kh * iw + kw + 1)) * x.ld) + 64
         min_rows, min_flops = x6_min if x6_min is not None else (pol.x6_min_rows, pol.x6_min_flops)
         if rows_all < min_rows or 2.0 * rows_all * cout * K < min_flops or x_bytes >= (1 << 31):
             w = w.f32
@@ -746,10 +765,12 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     h1t = h1 and one_product == "train"
     if h1:
         d.w_format |= W_F16X1 | (W_F16X1T if h1t else 0)
-    d.n, d.h, d.w, d.cin, d.cout = x.n, x.h, x.w, x.c, cout
+    d.n, d.h, d.w, d.cin, d.cout = x.n, ih, iw, x.c, cout
     d.kh, d.kw, d.stride, d.pad, d.ho, d.wo = kh, kw, stride, pad, ho, wo
     d.ldx = x.ld
     d.xmap = xmap if xmap is not None else x.nmap()
+    if up2_in and not h2:
+        return None                                    # (the mode exists in the fp16 scheme only: nothing launched)
     d.act, d.res_mode, d.split_k = act, res_mode, split_k
     d.transposed = 1 if transposed_out_hw is not None else 0
     d.groups, d.gx, d.gw, d.gp, d.grs, d.grm = groups, (gx or 0), (((w.h2_gstride if h2 else w.gstride) if x6 else npad * K) if groups > 1 else 0), (npad if groups > 1 else 0), grs, grm
@@ -842,6 +863,19 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
             aux.bn_partials = _p(bn_ws, torch.float64).value
             aux.bn_tiles_out = C.addressof(tiles)
             aux.bn_capacity = bn_ws.numel()
+    if up2_in:
+        if up2_out is not None and ((up2_out.n, up2_out.h, up2_out.w, up2_out.c) != (groups * x.n, ih, iw, x.c) or not up2_out.t.is_contiguous()):
+            raise RuntimeError("egorear_amd.conv2d: up2_out must be a dense (groups * n, 2 h, 2 w, cin) tensor")
+        aux.in_mode = IN_UP2_RELU
+        aux.in_up2_out = _p(up2_out.t).value if up2_out is not None else None
+        # decided on the host first: a call the library has no kernel for in this mode launches nothing
+        dev, probe = _DEV[0], ConvPlan()
+        rc = lib.egr_conv_plan(C.byref(d), _p(x.t), wptr, _p(scale), _p(shift), None, _p(rowscale), _p(rowmask, torch.uint8), None, yptr,
+                               ws_ptr, ws_n, C.byref(aux), C.byref(probe))
+        _DEV[0] = dev
+        if rc == EINVAL:
+            return None
+        _check(rc, "egr_conv_plan")
     fmt = ("h1 " if h1 else "h2 ") if h2 else ("x6 " if x6 else "")
     if PLAN_LOG is not None or (h1t and PROFILE is not None):
         dev, plan = _DEV[0], ConvPlan()
@@ -856,8 +890,11 @@ def conv2d(x: Img, w, cout: int, kh: int, kw: int, stride: int, pad: int, *, sca
     _launch("egr_conv2d_nhwc_f32", lib.egr_conv2d_nhwc_ex_f32, C.byref(d), _p(x.t), wptr, _p(scale), _p(shift),
             _p(res.t) if res is not None else None, _p(rowscale), _p(rowmask, torch.uint8), yptr, ws_ptr, ws_n,
             C.byref(aux) if aux is not None else None, _stream(),
-            flops=2.0 * M * cout * K * groups / (stride * stride if transposed_out_hw is not None else 1), nbytes=4.0 * groups * (M * cout + x.n * x.h * x.w * x.c + cout * K),
+            flops=2.0 * M * cout * K * groups / (stride * stride if transposed_out_hw is not None else 1),
+            nbytes=4.0 * groups * (M * cout + x.n * x.h * x.w * x.c + cout * K + (M * x.c if up2_out is not None else 0)),
             tag=f"{'T ' if transposed_out_hw is not None else ''}{fmt}G{groups} M{M} N{cout} K{K} k{kh}s{stride} cin{x.c}" if PROFILE is not None else "")
+    if up2_out is not None:
+        up2_out.tag(x.amax)    # bilinear interpolation (+ ReLU) is a convex combination: the input's record bounds it (as upsample2x)
     if ret is not None:
         ret.tag(amax_out)      # (also clears a stale record when this launch keeps none)
     if tiles is not None:

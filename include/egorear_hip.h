@@ -176,7 +176,21 @@ typedef struct {
     double* bn_partials;
     int32_t* bn_tiles_out;
     int64_t bn_capacity;
+    /* Input mode.  EGR_IN_PLAIN (0): x is the operand.  EGR_IN_UP2_RELU (1): x is a HALF-RESOLUTION tensor - d->h / 2 x d->w / 2
+     * pixels per image, pixel pitch ldx, images by xmap - and the operand is ReLU(bilinear x2(x)), align_corners=True, evaluated as
+     * the launch loads it: bit-identical to egr_upsample2x_nhwc_f32(relu = 1) followed by the plain launch, without the
+     * full-resolution tensor in between.  d describes the conv on the up-sampled image (h = ho, w = wo).  amax_in is the record of
+     * x: it bounds the interpolated operand.  in_up2_out (optional, 16-byte aligned): the launch also WRITES the operand, dense
+     * ((groups,) n, h, w, cin), for consumers that read it from memory - one pass over it instead of the up-sampling launch's write
+     * and this launch's read.
+     * Implemented by the streaming route alone: 1x1 / stride 1 / pad 0, cin 128, EGR_W_F16X2 (the one-product bits change nothing: that route has no such form), NHWC
+     * output, no residual / mask / row modifiers / statistics, w % 32 == 0 (a wave's 32 pixels lie in one row), enough rows for that
+     * route.  Every other call - other kernel sizes and strides, odd geometry, EGR_W_F32 / EGR_W_BF16X3, transposed, masked and
+     * statistics launches, out_nchw - returns EGR_EINVAL, from egr_conv_plan too, and launches nothing. */
+    int32_t in_mode;
+    float* in_up2_out;
 } egr_conv_aux;
+enum { EGR_IN_PLAIN = 0, EGR_IN_UP2_RELU = 1 };
 int egr_conv2d_nhwc_ex_f32(const egr_conv_desc* d, const float* x, const void* w, const float* scale, const float* shift,
                            const float* res, const float* rowscale, const uint8_t* rowmask, float* y, float* workspace,
                            size_t workspace_floats, const egr_conv_aux* aux /* NULL = egr_conv2d_nhwc_f32 */, void* stream);
@@ -238,6 +252,8 @@ typedef struct {
      *   F32_TILED / SPLIT_TILED  the tile configuration (egr_conv_force_config numbering)
      *   STREAM_1X1               100 KS + 10 NCF + RESK  (KS = cin / 16, NCF = 32-column fragments per workgroup, RESK 0 no residual /
      *                            1 residual / 2 residual upsampled on the fly)
+     *                            + 1000: egr_conv_aux.in_mode = EGR_IN_UP2_RELU (the operand up-sampled as it is loaded),
+     *                            + 2000: the same with the operand written out (in_up2_out)
      *   TAPX                     100 T + 10 R + cfg  (T 0 forward / 1 statistics epilogue / 2 masked data gradient, R 1 with residual,
      *                            cfg = the kernel's (tile, wave tile, stride) configuration 0, 1, 3 .. 7); + 1000: the one-product
      *                            form of a forward variant (EGR_W_F16X1) or of a training / data-gradient one (EGR_W_F16X1T)
