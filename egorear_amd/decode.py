@@ -32,6 +32,12 @@ an optional prior, minimised by Levenberg-Marquardt on `egr_skeleton_fit_f32` (D
 joint only one camera sees is placed by its ray and its bone.  `estimate_bone_lengths` (`egorear_amd::bone_lengths`) measures the bones
 of a clip, `resize_skeleton` (`egorear_amd::skeleton_resize`) is the reference's rescale along the chain, and
 `decode_joints_3d_skeleton` chains heat maps -> Joints2D -> Joints3D -> Skeleton3D.  None of them is differentiable.
+
+`smooth_trajectory` is the time axis: per joint of a clip a penalised least-squares track over the frames - the observations, a
+velocity and an acceleration penalty - on `egr_trajectory_smooth_f32` / `egr_trajectory_smooth_bwd_f32`, operators
+`egorear_amd::trajectory_smooth`, `egorear_amd::trajectory_smooth_bwd`: it fills the frames the triangulation gave up, optionally
+down-weights single-frame glitches by Huber reweighting, and is differentiable in its plain form with respect to the poses and their
+weights.  `decode_clip_3d` chains heat maps of a clip -> Joints3D per frame -> Track3D, three launches.
 """
 from __future__ import annotations
 
@@ -737,3 +743,146 @@ def decode_joints_3d_skeleton(heatmaps: torch.Tensor, cameras: Union[str, Sequen
     fit = fit_skeleton(joints2d.soft.detach(), joints2d.maxvals.detach(), cameras, bone_length, start, start_ok, parents, coord_trans_mat,
                        (H, W), threshold, bone_weight, prior_weight, iterations, min_det_ratio, camera_calib_file_dir_path)
     return fit, joints3d, joints2d
+
+
+# ---- temporal trajectory smoothing ---------------------------------------------------------------------------------------------------
+
+@torch.library.custom_op("egorear_amd::trajectory_smooth", mutates_args=(), device_types="cuda")
+def trajectory_smooth_op(pose: torch.Tensor, weight: Optional[torch.Tensor], obs: Optional[torch.Tensor], vel_weight: float,
+                         accel_weight: float, huber: float, reweights: int, max_gap: int
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose_out (N, T, J, 3) cm, valid (N, T, J) uint8, residual (N, T, J) cm, weight_out (N, T, J), energy (N, J)) of pose (N, T, J, 3),
+    weight (N, T, J) or None, obs (N, T, J) uint8 or None: egr_trajectory_smooth_f32.  pose_out is differentiable with
+    respect to pose and weight in the plain form (huber 0); with huber > 0 no output is."""
+    hip._trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap, "decode.trajectory_smooth", dense=False)
+    return hip.trajectory_smooth(_c(pose), _c(weight), _c(obs), vel_weight, accel_weight, huber, reweights, max_gap)
+
+
+@trajectory_smooth_op.register_fake
+def _trajectory_smooth_fake(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap):
+    N, T, J = hip._trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap, "decode.trajectory_smooth",
+                                       dense=False)
+    new = pose.new_empty
+    return new((N, T, J, 3)), new((N, T, J), dtype=torch.uint8), new((N, T, J)), new((N, T, J)), new((N, J))
+
+
+@torch.library.custom_op("egorear_amd::trajectory_smooth_bwd", mutates_args=(), device_types="cuda")
+def trajectory_smooth_bwd_op(pose: torch.Tensor, weight: Optional[torch.Tensor], obs: Optional[torch.Tensor], g_pose: torch.Tensor,
+                             vel_weight: float, accel_weight: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(g_pose_in (N, T, J, 3), g_weight (N, T, J) - or (0,) without a weight) from the cotangent of pose_out: the plain form only."""
+    gp = g_pose.to(torch.float32)
+    hip._trajectory_operands(pose, weight, obs, vel_weight, accel_weight, 0.0, 0, 0, "decode.trajectory_smooth_bwd", gp, dense=False)
+    g_in, g_weight = hip.trajectory_smooth_bwd(_c(pose), _c(weight), _c(obs), _c(gp), vel_weight, accel_weight)
+    return g_in, pose.new_empty((0,)) if g_weight is None else g_weight
+
+
+@trajectory_smooth_bwd_op.register_fake
+def _trajectory_smooth_bwd_fake(pose, weight, obs, g_pose, vel_weight, accel_weight):
+    N, T, J = hip._trajectory_operands(pose, weight, obs, vel_weight, accel_weight, 0.0, 0, 0, "decode.trajectory_smooth_bwd", g_pose,
+                                       dense=False)
+    return pose.new_empty((N, T, J, 3)), pose.new_empty((0,) if weight is None else (N, T, J))
+
+
+def _trj_setup_context(ctx, inputs, output):
+    pose, weight, obs, vel_weight, accel_weight, huber, _, _ = inputs
+    ctx.has_weight, ctx.has_obs = weight is not None, obs is not None
+    ctx.save_for_backward(*((pose,) + ((weight,) if ctx.has_weight else ()) + ((obs,) if ctx.has_obs else ())))
+    ctx.args = (vel_weight, accel_weight)
+    # (valid is not a floating-point tensor; with huber > 0 nothing is differentiable, as for the operators without a gradient)
+    ctx.mark_non_differentiable(*(output[2:] if huber == 0.0 else (output[0],) + tuple(output[2:])))
+
+
+def _trj_autograd(ctx, g_pose, g_valid, g_residual, g_weight_out, g_energy):
+    rest = list(ctx.saved_tensors)
+    pose = rest.pop(0)
+    weight = rest.pop(0) if ctx.has_weight else None
+    obs = rest.pop(0) if ctx.has_obs else None
+    if g_pose is None:
+        g_pose = torch.zeros_like(pose)
+    g_in, g_weight = trajectory_smooth_bwd_op(pose, weight, obs, g_pose, *ctx.args)
+    return g_in, (g_weight if ctx.has_weight else None), None, None, None, None, None, None
+
+
+trajectory_smooth_op.register_autograd(_trj_autograd, setup_context=_trj_setup_context)
+
+
+class Track3D(NamedTuple):
+    pose: torch.Tensor       # (N, T, J, 3) cm: the smoothed track, written for every frame of a solvable track; 0 for the others
+    valid: torch.Tensor      # (N, T, J) bool: the track is solvable and an observed frame is at most max_gap frames away
+    residual: torch.Tensor   # (N, T, J) cm: |pose - observation| at observed frames, 0 elsewhere
+    weight: torch.Tensor     # (N, T, J) the weights of the last solve: the base weight times the Huber factor
+    energy: torch.Tensor     # (N, J) the energy at the result
+
+
+def _trj_parameters(accel_weight, vel_weight, huber_cm, reweights, max_gap):
+    try:
+        return float(vel_weight), float(accel_weight), float(huber_cm), reweights, max_gap
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.decode.smooth_trajectory: accel_weight, vel_weight and huber_cm must be numbers, got "
+                         f"{accel_weight!r}, {vel_weight!r}, {huber_cm!r}") from None
+
+
+def smooth_trajectory(pose: torch.Tensor, weight: Optional[torch.Tensor] = None, observed: Optional[torch.Tensor] = None,
+                      accel_weight: float = 10.0, vel_weight: float = 0.0, huber_cm: float = 0.0, reweights: int = 0, max_gap: int = 8
+                      ) -> Track3D:
+    """pose (N, T, J, 3) cm - or (T, J, 3), one clip - with weight (N, T, J) (None: 1) and observed (N, T, J) bool / uint8 (None: every
+    frame; `Joints3D.valid` plugs in) -> Track3D(pose, valid, residual, weight, energy): per joint of every clip the track that minimises
+      sum_t w_t rho(|x_t - z_t|) + vel_weight sum |x_{t+1} - x_t|^2 + accel_weight sum |x_{t+1} - 2 x_t + x_{t-1}|^2
+    over the frames, w_t = weight_t where the frame is observed and pose and weight are finite (weight > 0), else 0: such a frame is a
+    gap, filled from its neighbours, and what stands in it is never read.  rho is the square, or with huber_cm > 0 Huber's function
+    at that radius, minimised by `reweights` (1..16) rounds of iteratively reweighted least squares after the plain solve - a
+    single-frame glitch is down-weighted instead of bending the track.  With vel_weight 0 a track needs two observed frames (every
+    frame where T <= 2), else one; a track without them gives zeros and valid False.  A frame is valid when an observed frame is at
+    most `max_gap` frames away; the pose is written for every frame regardless.  One launch.  In the plain form (huber_cm 0) the pose
+    is differentiable with respect to pose and weight; with huber_cm > 0 nothing is."""
+    vel_weight, accel_weight, huber_cm, reweights, max_gap = _trj_parameters(accel_weight, vel_weight, huber_cm, reweights, max_gap)
+    one = pose.dim() == 3
+    if one:
+        pose = pose.unsqueeze(0)
+        weight = None if weight is None else weight.unsqueeze(0)
+        observed = None if observed is None else observed.unsqueeze(0)
+    if observed is not None:
+        observed = _as_flags(observed)
+    hip._trajectory_operands(pose, weight, observed, vel_weight, accel_weight, huber_cm, reweights, max_gap, "decode.smooth_trajectory",
+                             dense=False)
+    hip._on_device("decode.smooth_trajectory", pose, weight, observed, exc=ValueError)
+    out, valid, residual, used, energy = trajectory_smooth_op(pose, weight, observed, vel_weight, accel_weight, huber_cm, reweights, max_gap)
+    track = Track3D(out, valid.view(torch.bool), residual, used, energy)
+    return Track3D(*(t.squeeze(0) for t in track)) if one else track
+
+
+def decode_clip_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None, beta: float = 100.0,
+                   threshold: float = 0.5, min_det_ratio: float = 1e-6, camera_calib_file_dir_path: Optional[str] = None,
+                   accel_weight: float = 10.0, vel_weight: float = 0.0, huber_cm: float = 0.0, reweights: int = 0, max_gap: int = 8
+                   ) -> Tuple[Joints3D, Track3D]:
+    """heatmaps (N, T, V, J, H, W) - or (T, V, J, H, W), one clip - -> (Joints3D, Track3D): `decode_joints_3d` on the N * T frames
+    (soft-argmax, triangulation), then `smooth_trajectory` of its pose with observed = its valid flags - three launches with nothing
+    between them, bit-identical to calling the pieces.  `coord_trans_mat` is (N, T, V, 4, 4) ((T, V, 4, 4) for one clip) or None.  A
+    joint that fewer than two cameras see for some frames is a gap that the neighbouring frames fill (Track3D.valid says how far they
+    are).  Both results come in the clip's shape: Joints3D fields (N, T, J, ...), Track3D as `smooth_trajectory` gives it.  In the plain
+    form the gradient of Track3D.pose reaches the heat maps through the three backward operators."""
+    what = "decode.decode_clip_3d"
+    one = heatmaps.dim() == 5
+    if one:
+        heatmaps = heatmaps.unsqueeze(0)
+        coord_trans_mat = None if coord_trans_mat is None else coord_trans_mat.unsqueeze(0)
+    if heatmaps.dim() != 6 or not 2 <= heatmaps.shape[2] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (N, T, V, J, H, W) or (T, V, J, H, W) with 2 to 4 views, got "
+                         f"{tuple(heatmaps.shape)}")
+    N, T, V, J = (int(v) for v in heatmaps.shape[:4])
+    if coord_trans_mat is not None and tuple(coord_trans_mat.shape) != (N, T, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(N, T, V, 4, 4)}, got {tuple(coord_trans_mat.shape)}")
+    # (what the smoother would refuse is refused before the soft-argmax runs)
+    vel_weight, accel_weight, huber_cm, reweights, max_gap = _trj_parameters(accel_weight, vel_weight, huber_cm, reweights, max_gap)
+    hip._trajectory_operands(heatmaps.new_empty((N, T, J, 3), device="meta"), None, None, vel_weight, accel_weight, huber_cm, reweights,
+                             max_gap, what, dense=False)
+    hip._on_device(what, heatmaps, coord_trans_mat, exc=ValueError)
+    frames = heatmaps.reshape((N * T,) + tuple(heatmaps.shape[2:]))
+    ctm = None if coord_trans_mat is None else coord_trans_mat.reshape(N * T, V, 4, 4)
+    joints3d, _ = decode_joints_3d(frames, cameras, ctm, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
+    track = smooth_trajectory(joints3d.pose.view(N, T, J, 3), None, joints3d.valid.view(N, T, J), accel_weight, vel_weight, huber_cm,
+                              reweights, max_gap)
+    clip = Joints3D(joints3d.pose.view(N, T, J, 3), joints3d.cost.view(N, T, J), joints3d.residual.view(N, T, V, J), joints3d.valid.view(N, T, J))
+    if one:
+        clip, track = Joints3D(*(t.squeeze(0) for t in clip)), Track3D(*(t.squeeze(0) for t in track))
+    return clip, track

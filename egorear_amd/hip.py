@@ -191,6 +191,7 @@ EXPORTS = [
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
     "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
     "egr_peaks_f32", "egr_consensus_f32", "egr_skeleton_fit_f32", "egr_bone_lengths_f32", "egr_skeleton_resize_f32",
+    "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32",
 ]
 
 
@@ -325,6 +326,8 @@ def _load() -> C.CDLL:
                                          vp, vp, vp, vp, vp]
     lib.egr_bone_lengths_f32.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.egr_skeleton_resize_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.egr_trajectory_smooth_f32.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.egr_trajectory_smooth_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -1720,6 +1723,86 @@ def skeleton_resize(pose: torch.Tensor, valid: torch.Tensor, bone_length: torch.
             B, J,
             _p(out), _stream(), nbytes=B * J * 29.0)
     return out
+
+
+TRAJECTORY_MAX_T = 4096           # frames of one clip of egr_trajectory.hip
+TRAJECTORY_MAX_REWEIGHTS = 16
+TRAJECTORY_FWD_SLOTS, TRAJECTORY_BWD_SLOTS = 5, 8      # fp64 workspace planes of T * N * J: the two sub-diagonals and 3 / 6 right-hand sides
+
+
+def _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap, what: str, g_pose=None, dense: bool = True):
+    """(N, T, J) of a trajectory launch; every shape / dtype / parameter error as ValueError."""
+    if pose.dim() != 4 or pose.shape[-1] != 3:
+        raise ValueError(f"egorear_amd.{what}: pose must be (N, T, J, 3), got {tuple(pose.shape)}")
+    N, T, J = (int(v) for v in pose.shape[:3])
+    if N < 1 or T < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty pose {tuple(pose.shape)}")
+    if T > TRAJECTORY_MAX_T:
+        raise ValueError(f"egorear_amd.{what}: at most {TRAJECTORY_MAX_T} frames a clip are supported, got {T}")
+    if N * T * J >= 1 << 31:
+        raise ValueError(f"egorear_amd.{what}: N * T * J must stay below 2^31, got {tuple(pose.shape)}")
+    if weight is not None and tuple(weight.shape) != (N, T, J):
+        raise ValueError(f"egorear_amd.{what}: weight must be {(N, T, J)}, got {tuple(weight.shape)}")
+    if obs is not None:
+        _flags(what, obs, (N, T, J), "observed")
+    _float32(what, (pose, "pose"), (weight, "weight"))
+    _non_negative(what, "vel_weight", vel_weight)
+    _non_negative(what, "accel_weight", accel_weight)
+    if not (vel_weight > 0.0 or accel_weight > 0.0):
+        raise ValueError(f"egorear_amd.{what}: vel_weight and accel_weight must not both be zero")
+    _non_negative(what, "huber", huber)
+    if not _int_in(reweights, 0, TRAJECTORY_MAX_REWEIGHTS):
+        raise ValueError(f"egorear_amd.{what}: reweights must be an integer in 0..{TRAJECTORY_MAX_REWEIGHTS}, got {reweights!r}")
+    if (reweights > 0) != (huber > 0.0):
+        raise ValueError(f"egorear_amd.{what}: huber > 0 and reweights > 0 go together (the plain form has both 0), got huber {huber!r}, "
+                         f"reweights {reweights!r}")
+    if not _int_in(max_gap, 0, (1 << 31) - 1):
+        raise ValueError(f"egorear_amd.{what}: max_gap must be a non-negative integer, got {max_gap!r}")
+    _cotangents(what, (g_pose, (N, T, J, 3), "g_pose"))
+    _contiguous(what, dense, (pose, "pose"), (weight, "weight"), (obs, "observed"), (g_pose, "g_pose"))
+    return N, T, J
+
+
+def trajectory_smooth(pose: torch.Tensor, weight: Optional[torch.Tensor] = None, obs: Optional[torch.Tensor] = None, vel_weight: float = 0.0,
+                      accel_weight: float = 10.0, huber: float = 0.0, reweights: int = 0, max_gap: int = 8):
+    """pose (N,T,J,3) cm, weight (N,T,J) | None (1), obs (N,T,J) u8 / bool | None (every frame) -> pose_out (N,T,J,3), valid (N,T,J) u8,
+    residual (N,T,J), weight_out (N,T,J), energy (N,J): egr_trajectory_smooth_f32, the penalised least-squares trajectory of every joint
+    of every clip (include/egorear_hip.h states the energy, the Huber reweighting and the validity rule).  The fp64 workspace of the
+    elimination is allocated here, like the outputs."""
+    N, T, J = _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap, "trajectory_smooth")
+    _on_device("trajectory_smooth", pose, weight, obs)
+    if obs is not None:
+        obs = _flags("trajectory_smooth", obs, (N, T, J), "observed")
+    dev = pose.device
+    ws = torch.empty((TRAJECTORY_FWD_SLOTS, T, N * J), device=dev, dtype=torch.float64)
+    pose_out = torch.empty((N, T, J, 3), device=dev, dtype=torch.float32)
+    valid = torch.empty((N, T, J), device=dev, dtype=torch.uint8)
+    residual, weight_out = (torch.empty((N, T, J), device=dev, dtype=torch.float32) for _ in range(2))
+    energy = torch.empty((N, J), device=dev, dtype=torch.float32)
+    sweeps = 2.0 * (reweights + 1)
+    _launch("egr_trajectory_smooth_f32", lib.egr_trajectory_smooth_f32, _p(pose), _p(weight), _p(obs, torch.uint8), N, T, J, float(vel_weight),
+            float(accel_weight), float(huber), int(reweights), int(max_gap), _p(ws, torch.float64), _p(pose_out), _p(valid, torch.uint8),
+            _p(residual), _p(weight_out), _p(energy), _stream(), flops=N * T * J * sweeps * 40.0,
+            nbytes=N * T * J * (sweeps * (40.0 + 17.0) + 21.0))
+    return pose_out, valid, residual, weight_out, energy
+
+
+def trajectory_smooth_bwd(pose: torch.Tensor, weight: Optional[torch.Tensor], obs: Optional[torch.Tensor], g_pose: torch.Tensor,
+                          vel_weight: float = 0.0, accel_weight: float = 10.0):
+    """Gradients of the plain form's pose_out with respect to pose and weight, (N,T,J,3) and (N,T,J) (None without a weight):
+    egr_trajectory_smooth_bwd_f32 (the factorisation is recomputed from the operands)."""
+    N, T, J = _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, 0.0, 0, 0, "trajectory_smooth_bwd", g_pose)
+    _on_device("trajectory_smooth_bwd", pose, weight, obs, g_pose)
+    if obs is not None:
+        obs = _flags("trajectory_smooth_bwd", obs, (N, T, J), "observed")
+    dev = pose.device
+    ws = torch.empty((TRAJECTORY_BWD_SLOTS, T, N * J), device=dev, dtype=torch.float64)
+    g_in = torch.empty((N, T, J, 3), device=dev, dtype=torch.float32)
+    g_weight = None if weight is None else torch.empty((N, T, J), device=dev, dtype=torch.float32)
+    _launch("egr_trajectory_smooth_bwd_f32", lib.egr_trajectory_smooth_bwd_f32, _p(pose), _p(weight), _p(obs, torch.uint8), _p(g_pose), N, T, J,
+            float(vel_weight), float(accel_weight), _p(ws, torch.float64), _p(g_in), _p(g_weight), _stream(), flops=N * T * J * 2.0 * 70.0,
+            nbytes=N * T * J * (2.0 * 64.0 + 2.0 * 17.0 + 12.0 + 16.0))
+    return g_in, g_weight
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -620,6 +620,40 @@ int egr_bone_lengths_f32(const float* pose, const uint8_t* valid, const int32_t*
 int egr_skeleton_resize_f32(const float* pose, const uint8_t* valid, const int32_t* parents /* J, host */, const float* bone_length,
                             int32_t bone_length_per_frame, int32_t B, int32_t J, float* out /* B x J x 3 */, void* stream);
 
+/* Temporal trajectory smoothing of 3-D joints over a clip.  A track is one joint of one clip: observations z_t =
+ * pose[n, t, j, :] (cm), t = 0..T-1, with base weights  w_t = weight_t [obs_t != 0] [z_t and weight_t finite, weight_t > 0]  (weight
+ * NULL: 1; obs NULL: every frame; egr_triangulate_f32's ok plugs in as obs).  A frame with w_t = 0 is never read into arithmetic: what
+ * is planted there reaches no output.  The smoothed track minimises
+ *   E(x) = sum_t w_t rho(|x_t - z_t|) + vel_weight sum_{t=0}^{T-2} |x_{t+1} - x_t|^2 + accel_weight sum_{t=1}^{T-2} |x_{t+1} - 2 x_t + x_{t-1}|^2,
+ * rho(r) = r^2 with huber == 0;  r^2 for r <= huber and 2 huber r - huber^2 beyond with huber > 0.
+ *   Plain form (huber == 0, reweights == 0): x solves A x = W z, A = W + vel_weight D1^T D1 + accel_weight D2^T D2 - symmetric,
+ *   positive definite, pentadiagonal, shared by the three coordinates.
+ *   Robust form (huber > 0, reweights = K in 1..16): s(0) = 1; x(k) solves the plain problem with the weights w_t s_t(k);
+ *   s_t(k+1) = min(1, huber / |x_t(k) - z_t|); the result is x(K) - K + 1 solves, always, no convergence test.  A majorise-minimise
+ *   step: E does not increase from one k to the next.
+ *   A track is solvable (A positive definite), decided from the base weights: with vel_weight > 0, one observed frame or more; with
+ *   vel_weight == 0 and T >= 3, two or more; with vel_weight == 0 and T <= 2, every frame.  A track that is not solvable gives pose 0,
+ *   valid 0, residual 0, weight_out 0 and energy 0.
+ * pose_out (N, T, J, 3): written for every frame of a solvable track; valid (N, T, J): 1 iff the track is solvable and the nearest
+ * observed frame is at most max_gap frames away; residual (N, T, J): |x_t - z_t| at observed frames, 0 elsewhere; weight_out
+ * (N, T, J): w_t s_t(K), the weights of the last solve; energy (N, J): E at the result, rho as configured, with the base weights.
+ * workspace: 5 * T * N * J doubles, contents unspecified before and after.  The parameters are taken as fp32.
+ * One lane per track, a banded LDL^T along t in fp64 on the fp32 operands, every solve and the energy pass in the one launch; no
+ * atomics, a fixed order: the same bits every run, alone or in a batch.  Latency-bound: a dependent fp64 chain of length T per sweep.
+ * EGR_EINVAL: N or J < 1, T outside 1..4096, N*T*J >= 2^31, a weight negative or not finite or both zero, huber negative or not
+ * finite, reweights outside 0..16, reweights > 0 with huber == 0 or huber > 0 with reweights == 0, max_gap < 0. */
+int egr_trajectory_smooth_f32(const float* pose, const float* weight /* nullable */, const uint8_t* obs /* nullable */, int32_t N, int32_t T,
+                              int32_t J, float vel_weight, float accel_weight, float huber, int32_t reweights, int32_t max_gap,
+                              double* workspace /* 5 x T x N x J */, float* pose_out /* N x T x J x 3 */, uint8_t* valid /* N x T x J */,
+                              float* residual /* N x T x J */, float* weight_out /* N x T x J */, float* energy /* N x J */, void* stream);
+/* Backward of the plain form: with u = A^-1 g_pose_out (the same factorisation, recomputed from the operands, on three more
+ * right-hand sides)  g_pose[t] = w_t u_t  and  g_weight[t] = [observed_t] u_t . (z_t - x_t)  (g_weight NULL to skip); zeros for a track
+ * that is not solvable.  workspace: 8 * T * N * J doubles.  EGR_EINVAL as above. */
+int egr_trajectory_smooth_bwd_f32(const float* pose, const float* weight /* nullable */, const uint8_t* obs /* nullable */,
+                                  const float* g_pose_out /* N x T x J x 3 */, int32_t N, int32_t T, int32_t J, float vel_weight,
+                                  float accel_weight, double* workspace /* 8 x T x N x J */, float* g_pose /* N x T x J x 3 */,
+                                  float* g_weight /* N x T x J, nullable */, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
