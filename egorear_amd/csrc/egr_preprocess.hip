@@ -324,7 +324,11 @@ __global__ __launch_bounds__(FTH) void resize_fused_kernel(const uint8_t* __rest
     }
 }
 
+int g_last_preprocess_kernel = 0;   // diagnostic (tests): 0 = LDS horizontal pass, 1 = aligned-dword, 2 = generic, 3 = fused
+
 }  // namespace
+
+extern "C" int egr_preprocess_last_kernel(void) { return g_last_preprocess_kernel; }
 
 // largest source band (rows) any 32-row output band of the vertical pass touches; the tables are host arrays here
 extern "C" int egr_preprocess_band_rows(const int32_t* bounds_v_host, int32_t oh) {
@@ -362,7 +366,9 @@ extern "C" int egr_preprocess_fused_u8_f32(const uint8_t* src, int32_t n, int32_
     const int bands = (oh + FOB - 1) / FOB;
     hipLaunchKernelGGL(resize_fused_kernel, dim3((unsigned)(n * bands)), dim3(FTH), lds_b, (hipStream_t)stream, src, dst, u8out, h, w, oh, ow, bounds_h,
                        coef_h, ksize_h, bounds_v, coef_v, ksize_v, band_rows, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
-    return egr_launch_status();
+    const int rc = egr_launch_status();
+    if (!rc) g_last_preprocess_kernel = 3;
+    return rc;
 }
 
 extern "C" int egr_preprocess_u8_f32(const uint8_t* src, int32_t n, int32_t h, int32_t w, int32_t oh, int32_t ow,
@@ -371,26 +377,33 @@ extern "C" int egr_preprocess_u8_f32(const uint8_t* src, int32_t n, int32_t h, i
                                      const float* stdv, uint8_t* tmp, float* dst, uint8_t* u8out, void* stream) {
     if (!src || !bounds_h || !coef_h || !bounds_v || !coef_v || !mean || !stdv || !tmp || !dst) return EGR_ENULL;
     if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ksize_h <= 0 || ksize_v <= 0) return EGR_EINVAL;
-    if (ow % 4 != 0 || ksize_h > MAXK || ksize_v > MAXK || ((uintptr_t)src & 3) || ((uintptr_t)tmp & 3) || ((uintptr_t)dst & 15))
-        return EGR_EINVAL;  // 4 output columns per thread, aligned dword / 16-byte accesses
+    if (ow % 4 != 0 || ksize_h > MAXK || ksize_v > MAXK || ((uintptr_t)tmp & 3) || ((uintptr_t)dst & 15))
+        return EGR_EINVAL;  // vertical pass: 4 output columns per thread, aligned dword loads of tmp, 16-byte stores to dst
     hipStream_t s = (hipStream_t)stream;
     int64_t t1 = (int64_t)n * h * ow, t2 = (int64_t)n * oh * (ow / 4);
     if (t1 >= (1LL << 31) * 256 || t2 >= (1LL << 31) * 256) return EGR_EINVAL;
     const int in_b = RH * w * 3, out_b = RH * ow * 3;
     const size_t lds_b = (size_t)((in_b + 64 + 15) & ~15) + (size_t)out_b;
+    int route;
     if (ksize_h <= 16 && h % RH == 0 && in_b % 16 == 0 && out_b % 16 == 0 && lds_b <= 64 * 1024 && ((uintptr_t)src & 15) == 0 &&
-        ((uintptr_t)tmp & 15) == 0)
+        ((uintptr_t)tmp & 15) == 0) {
+        route = 0;
         hipLaunchKernelGGL(resize_h_lds_kernel, dim3((unsigned)((int64_t)n * h / RH)), dim3(256), lds_b, s, src, tmp, (int64_t)n * h, w, ow,
                            bounds_h, coef_h, ksize_h);
-    else if (ksize_h <= 16 && ((int64_t)h * w * 3) % 4 == 0)
+    } else if (ksize_h <= 16 && ((int64_t)h * w * 3) % 4 == 0 && ((uintptr_t)src & 3) == 0) {   // the kernel reads src as aligned dwords
+        route = 1;
         hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, s, src, tmp, n, h, w, ow, bounds_h,
                            coef_h, ksize_h);
-    else
+    } else {
+        route = 2;
         hipLaunchKernelGGL(resize_h_generic_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, s, src, tmp, n, h, w, ow,
                            bounds_h, coef_h, ksize_h);
+    }
     int rc = egr_launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(resize_v_norm_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, tmp, dst, n, h, ow, oh,
                        bounds_v, coef_v, ksize_v, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], u8out);
-    return egr_launch_status();
+    rc = egr_launch_status();
+    if (!rc) g_last_preprocess_kernel = route;
+    return rc;
 }

@@ -182,7 +182,7 @@ EXPORTS = [
     "egr_fisheye_project_f32", "egr_linear_smallk_f32", "egr_jqa_sum_f32", "egr_tokens_to_nhwc_f32", "egr_version",
     "egr_device_arch", "egr_conv_force_config", "egr_preprocess_u8_f32", "egr_pose_metrics_f32", "egr_gt_heatmap_f32", "egr_conv_debug_stamps", "egr_conv2d_wgrad_f32", "egr_conv2d_masked_f32", "egr_up2_relu_head_f32",
     "egr_msda_fwd_f32", "egr_msda_bwd_f32", "egr_w6_elems", "egr_pack_w6_f32", "egr_pack_w6_many_f32", "egr_joint_layer_f32",
-    "egr_preprocess_fused_u8_f32", "egr_preprocess_band_rows", "egr_conv_set_persist", "egr_stem_conv7x7_pool_f32",
+    "egr_preprocess_fused_u8_f32", "egr_preprocess_band_rows", "egr_preprocess_last_kernel", "egr_conv_set_persist", "egr_stem_conv7x7_pool_f32",
     "egr_stem_w6_bytes", "egr_pack_stem_w6_f32", "egr_stem_conv7x7_x6_f32", "egr_wgrad_last_kernel", "egr_conv_last_kernel", "egr_conv_set_tap", "egr_conv_set_tapx", "egr_conv_set_splitk_fused", "egr_fisheye_project2_f32", "egr_pack_layer_w_f32", "egr_pack_layer_wh2_f32",
     "egr_conv2d_nhwc_ex_f32", "egr_wh2_elems", "egr_pack_wh2_f32", "egr_absmax_f32", "egr_stem_conv7x7_x6_ex_f32", "egr_stem_wh2_bytes", "egr_pack_stem_wh2_f32", "egr_stem_conv7x7_h2_f32",
     "egr_pack_wh2_many_f32", "egr_conv2d_masked_ex_f32", "egr_conv2d_wgrad_ex_f32", "egr_wgrad_last_h2", "egr_wgrad_last_planes",
@@ -231,6 +231,8 @@ class ConvPlan(C.Structure):
 
 # egr_conv_route: the values of ConvPlan.route and of conv_last_kernel()
 ROUTE_F32_TILED, ROUTE_SPLIT_TILED, ROUTE_TAP, ROUTE_TAP2, ROUTE_STREAM_1X1, ROUTE_SMALL_F32, ROUTE_TAPX = range(7)
+# the values of egr_preprocess_last_kernel(): which horizontal-pass kernel (or the fused one) the last successful call launched
+PRE_ROUTE_LDS, PRE_ROUTE_DWORD, PRE_ROUTE_GENERIC, PRE_ROUTE_FUSED = range(4)
 # egr_conv_desc.w_format bits the wrappers set by name (include/egorear_hip.h)
 W_F16X2, W_F16X1, W_F16X1T = 4, 8, 16
 
@@ -364,6 +366,7 @@ def _load() -> C.CDLL:
     lib.egr_pack_layer_wh2_f32.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.egr_preprocess_fused_u8_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.egr_preprocess_band_rows.argtypes = [vp, i32]
+    lib.egr_preprocess_last_kernel.argtypes = []
     lib.egr_preprocess_u8_f32.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # fail at import if a symbol is missing

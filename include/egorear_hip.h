@@ -813,11 +813,14 @@ int egr_tokens_to_nhwc_f32(const float* x, float* y, int32_t b, int32_t j, int32
  * datasets/ego4view_syn/ego4view_syn_pose3d.py:41-44,159-162: src (n, h, w, 3) uint8 -> dst (n, 3, oh, ow) fp32.
  * bounds_* (out, 2) [first tap, tap count] and coef_* (out, ksize) 22-bit fixed-point weights are Pillow's
  * precompute_coeffs / normalize_coeffs_8bpc tables (host-computed); tmp (n, h, ow, 3) uint8 scratch;
- * mean / stdv: 3 HOST floats; u8out (n, oh, ow, 3) optional uint8 copy of the resized image (NULL to skip). */
+ * mean / stdv: 3 HOST floats; u8out (n, oh, ow, 3) optional uint8 copy of the resized image (NULL to skip).
+ * Alignment: tmp 4 bytes, dst 16 bytes, ow % 4 == 0 (EGR_EINVAL otherwise); src may sit at any byte address. */
 int egr_preprocess_u8_f32(const uint8_t* src, int32_t n, int32_t h, int32_t w, int32_t oh, int32_t ow,
                           const int32_t* bounds_h, const int32_t* coef_h, int32_t ksize_h,
                           const int32_t* bounds_v, const int32_t* coef_v, int32_t ksize_v,
                           const float* mean, const float* stdv, uint8_t* tmp, float* dst, uint8_t* u8out, void* stream);
+/* diagnostic (tests): the kernel of the last successful launch - 0 LDS horizontal pass, 1 aligned-dword, 2 generic, 3 fused. */
+int egr_preprocess_last_kernel(void);
 
 /* The same conversion as ONE launch: the horizontally resized uint8 rows of a 32-output-row band stay in LDS (no intermediate in
  * HBM, no `tmp`).  band_rows = egr_preprocess_band_rows(host copy of bounds_v, oh).  Returns EGR_EINVAL without launching when the
