@@ -38,6 +38,11 @@ velocity and an acceleration penalty - on `egr_trajectory_smooth_f32` / `egr_tra
 `egorear_amd::trajectory_smooth`, `egorear_amd::trajectory_smooth_bwd`: it fills the frames the triangulation gave up, optionally
 down-weights single-frame glitches by Huber reweighting, and is differentiable in its plain form with respect to the poses and their
 weights.  `decode_clip_3d` chains heat maps of a clip -> Joints3D per frame -> Track3D, three launches.
+
+`refine_rig` calibrates the rig itself: from the decoded joints of a clip, per camera the rotation about its own centre that makes the
+views' rays meet best, by Levenberg-Marquardt on `egr_rig_refine_f32` (DESIGN.md 5t), operator `egorear_amd::rig_refine`, not
+differentiable.  Its `coord_trans_mat` goes to every function above in place of the given one; `apply_rig_correction` composes a fitted
+correction with another clip's matrices, and `calibrate_rig` chains heat maps -> Joints2D -> RigFit.
 """
 from __future__ import annotations
 
@@ -886,3 +891,127 @@ def decode_clip_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_
     if one:
         clip, track = Joints3D(*(t.squeeze(0) for t in clip)), Track3D(*(t.squeeze(0) for t in track))
     return clip, track
+
+
+# ---- rig self-calibration ------------------------------------------------------------------------------------------------------------
+
+@torch.library.custom_op("egorear_amd::rig_refine", mutates_args=(), device_types="cuda")
+def rig_refine_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], fixed: Sequence[int], sx: float,
+                  sy: float, threshold: float, min_det_ratio: float, prior_weight: float, iterations: int
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                             torch.Tensor]:
+    """(rotation (V, 3) rad, matrix (V, 3, 3), coord_trans_mat (B, V, 4, 4), cost0 (1), cost (1), pairs (1) int32, steps (1) int32,
+    grad (1), valid (1) uint8) of the triangulation's operands - ctm (B, V, 4, 4), (1, V, 4, 4) or None - and V flags, the held cameras:
+    egr_rig_refine_f32.  No output is differentiable."""
+    hip._rig_operands(coords, conf, cams, ctm, fixed, sx, sy, min_det_ratio, prior_weight, iterations, "decode.rig_refine", dense=False)
+    return hip.rig_refine(_c(coords), _c(conf), _c(cams), _c(ctm), fixed, sx, sy, threshold, min_det_ratio, prior_weight, iterations)
+
+
+@rig_refine_op.register_fake
+def _rig_refine_fake(coords, conf, cams, ctm, fixed, sx, sy, threshold, min_det_ratio, prior_weight, iterations):
+    B, V, J, _, _ = hip._rig_operands(coords, conf, cams, ctm, fixed, sx, sy, min_det_ratio, prior_weight, iterations, "decode.rig_refine",
+                                      dense=False)
+    new = coords.new_empty
+    return (new((V, 3)), new((V, 3, 3)), new((B, V, 4, 4)), new((1,)), new((1,)), new((1,), dtype=torch.int32), new((1,), dtype=torch.int32),
+            new((1,)), new((1,), dtype=torch.uint8))
+
+
+rig_refine_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+
+
+class RigFit(NamedTuple):
+    rotation: torch.Tensor          # (V, 3) rotation vector of every camera's correction, rad; 0 for a held camera
+    matrix: torch.Tensor            # (V, 3, 3) the same as matrices dR: p_cam' = dR (R p + t)
+    coord_trans_mat: torch.Tensor   # (B, V, 4, 4) [dR 0; 0 1] M: what every decode function takes with the same `cameras`
+    cost0: torch.Tensor             # () weighted mean squared ray distance over the counted pairs at the given rig, cm^2
+    cost: torch.Tensor              # () the same at the result, <= cost0
+    pairs: torch.Tensor             # () int32 (frame, joint) pairs that counted
+    steps: torch.Tensor             # () int32 iterations whose step was kept
+    grad: torch.Tensor              # () largest |dE/d rotation| component over the free cameras at the result
+    valid: torch.Tensor             # () bool: false when no pair counts or the clip does not fix the rotations (then: the identity)
+
+
+def refine_rig(coords: torch.Tensor, conf: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+               heatmap_size: Tuple[float, float] = (64, 64), threshold: float = 0.5, min_det_ratio: float = 1e-6, fixed=None,
+               prior_weight: float = 0.0, iterations: int = 8, camera_calib_file_dir_path: Optional[str] = None) -> RigFit:
+    """coords (B, V, J, 2), conf (B, V, J) of a clip, `cameras`, `heatmap_size`, `threshold`, `min_det_ratio` as for
+    `triangulate_joints`; `coord_trans_mat` None (the ego4view_syn rig), (B, V, 4, 4) per frame or (1, V, 4, 4) for the clip
+    -> RigFit: per camera the rotation about its own centre that makes the views' rays meet best over the whole clip,
+      sum over (frame, joint) of min_p sum_v conf_v dist^2(p, ray_v rotated) + prior_weight * sum_v |dR_v - I|_F^2,
+    minimised over the cameras that are not `fixed` (V flags or a (V,) bool tensor in host memory; None holds view 0 alone, which
+    removes the rig's common rotation; all held is legal and returns the identity).  Rotations are what drifts on a head-mounted rig
+    and what this cost can see: translations are not refined - scaling the camera centres and the points together shrinks every ray
+    distance, so free translations would collapse the rig.  A pair counts when the triangulation at the given rig is valid for it.
+    `iterations` (1..256) Levenberg-Marquardt steps are tried, always; convergence is quadratic where the rays can meet (4 to 6 reach
+    fp32 stationarity from 0.03 rad) and `grad` reports how stationary the result is.  `RigFit.coord_trans_mat` goes to every decode
+    function in place of the given one.  Coordinate noise biases the fit - rays that meet closer to the cameras miss by less - by
+    about 0.8 rad per squared heat-map pixel however long the clip: the joints should be better than 0.15 px for a
+    0.03 rad drift, or `prior_weight` should hold the fit near the given rig.  Outliers are the caller's business: `select_consistent` yields coords / conf with out-voted
+    views at zero confidence, which this function excludes like any view below `threshold`; there is no second robust scheme here.
+    1 + 2 (iterations + 1) launches, no host synchronisation, bit-reproducible; nothing here is differentiable."""
+    sx, sy = _scales(heatmap_size)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, coords.device)
+    if coords.dim() != 4:
+        raise ValueError(f"egorear_amd.decode.refine_rig: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    flags = [int(f) for f in hip._rig_operands(coords, conf, cams, coord_trans_mat, fixed, sx, sy, float(min_det_ratio), float(prior_weight),
+                                               iterations, "decode.refine_rig", dense=False)[3]]
+    hip._on_device("decode.refine_rig", coords, conf, coord_trans_mat, exc=ValueError)
+    rotation, matrix, ctm, cost0, cost, pairs, steps, grad, valid = rig_refine_op(
+        coords, conf, cams, coord_trans_mat, flags, sx, sy, float(threshold), float(min_det_ratio), float(prior_weight), iterations)
+    return RigFit(rotation, matrix, ctm, cost0.view(()), cost.view(()), pairs.view(()), steps.view(()), grad.view(()),
+                  valid.view(torch.bool).view(()))
+
+
+def apply_rig_correction(matrix: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor], B: int,
+                         camera_calib_file_dir_path: Optional[str] = None) -> torch.Tensor:
+    """`RigFit.matrix` (V, 3, 3) of one clip applied to the rig of another: [dR 0; 0 1] M_v as fp32 (B, V, 4, 4), M the given
+    `coord_trans_mat` ((B, V, 4, 4) or (1, V, 4, 4)) or, for None, the ego4view_syn rig written as matrices (the flip on the diagonal,
+    the offsets in m, fp32) - the composition `refine_rig` returns, bit for bit, alone: float64 torch operations rounded once.  Not
+    differentiable."""
+    what = "decode.apply_rig_correction"
+    if matrix.dim() != 3 or tuple(matrix.shape[1:]) != (3, 3) or not 2 <= matrix.shape[0] <= 4 or matrix.dtype != torch.float32:
+        raise ValueError(f"egorear_amd.{what}: matrix must be a float32 (V, 3, 3) with 2 to 4 views, got {matrix.dtype} {tuple(matrix.shape)}")
+    V = int(matrix.shape[0])
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise ValueError(f"egorear_amd.{what}: B must be a positive integer, got {B!r}")
+    if coord_trans_mat is not None and (tuple(coord_trans_mat.shape) not in ((B, V, 4, 4), (1, V, 4, 4)) or coord_trans_mat.dtype != torch.float32):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be a float32 {(B, V, 4, 4)} or {(1, V, 4, 4)}, got "
+                         f"{coord_trans_mat.dtype} {tuple(coord_trans_mat.shape)}")
+    hip._on_device(what, matrix, coord_trans_mat, exc=ValueError)
+    with torch.no_grad():
+        if coord_trans_mat is None:
+            rec = _ray_records(cameras, camera_calib_file_dir_path, matrix.device).double()
+            if tuple(rec.shape) != (V, hip.RAY_REC):
+                raise ValueError(f"egorear_amd.{what}: {V} matrices for {rec.shape[0]} cameras")
+            f = 1.0 - 2.0 * (rec[:, 26] != 0).double()
+            m = torch.diag_embed(torch.stack((f, f, torch.ones_like(f), torch.ones_like(f)), -1))
+            m[:, :3, 3] = (rec[:, 27:30] * 0.01).float().double()        # (fp32, as a caller would pass the rig)
+            m = m.unsqueeze(0)
+        else:
+            m = coord_trans_mat.double()
+        left = torch.zeros((V, 4, 4), dtype=torch.float64, device=matrix.device)
+        left[:, :3, :3] = matrix.double()
+        left[:, 3, 3] = 1.0
+        out = (left.unsqueeze(0).unsqueeze(-1) * m.unsqueeze(-3)).sum(-2)
+        return out.expand(B, V, 4, 4).float().contiguous()
+
+
+def calibrate_rig(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None, beta: float = 100.0,
+                  threshold: float = 0.5, min_det_ratio: float = 1e-6, fixed=None, prior_weight: float = 0.0, iterations: int = 8,
+                  camera_calib_file_dir_path: Optional[str] = None) -> Tuple[RigFit, Joints2D]:
+    """heatmaps (B, V, J, H, W) of a clip -> (RigFit, Joints2D): `decode_joints_2d` (soft-argmax at `beta`), then `refine_rig` on its
+    sub-pixel joints weighted by the maps' maxima, with nothing on the host in between - bit-identical to calling the two."""
+    what = "decode.calibrate_rig"
+    # (the soft-argmax takes any V: what the fit would refuse is refused before it runs)
+    if heatmaps.dim() != 5 or not 2 <= heatmaps.shape[1] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (B, V, J, H, W) with 2 to 4 views, got {tuple(heatmaps.shape)}")
+    _check(heatmaps, float(beta), MODE_SOFTMAX, dims=5, what="calibrate_rig")
+    B, V, J, H, W = (int(v) for v in heatmaps.shape)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
+    hip._rig_operands(heatmaps.new_empty((B, V, J, 2), device="meta"), heatmaps.new_empty((B, V, J), device="meta"), cams, coord_trans_mat, fixed,
+                      1.0 / W, 1.0 / H, float(min_det_ratio), float(prior_weight), iterations, what, dense=False)
+    hip._on_device(what, heatmaps, coord_trans_mat, exc=ValueError)
+    joints2d = decode_joints_2d(heatmaps, beta=beta, threshold=threshold)
+    fit = refine_rig(joints2d.soft.detach(), joints2d.maxvals.detach(), cameras, coord_trans_mat, (H, W), threshold, min_det_ratio, fixed,
+                     prior_weight, iterations, camera_calib_file_dir_path)
+    return fit, joints2d

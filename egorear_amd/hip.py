@@ -191,7 +191,7 @@ EXPORTS = [
     "egr_conv_plan", "egr_soft_argmax_f32", "egr_soft_argmax_bwd_f32", "egr_coord_l1_f32",
     "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
     "egr_peaks_f32", "egr_consensus_f32", "egr_skeleton_fit_f32", "egr_bone_lengths_f32", "egr_skeleton_resize_f32",
-    "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32",
+    "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32", "egr_rig_refine_f32", "egr_rig_refine_workspace_bytes",
 ]
 
 
@@ -330,6 +330,10 @@ def _load() -> C.CDLL:
     lib.egr_skeleton_resize_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.egr_trajectory_smooth_f32.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.egr_trajectory_smooth_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
+    lib.egr_rig_refine_workspace_bytes.restype = C.c_int64
+    lib.egr_rig_refine_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.egr_rig_refine_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, i32, f32, i32, vp, i64, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -371,7 +375,7 @@ def _load() -> C.CDLL:
     for name in EXPORTS:
         getattr(lib, name)  # fail at import if a symbol is missing
         if name not in ("egr_version", "egr_w6_elems", "egr_stem_w6_bytes", "egr_wh2_elems", "egr_stem_wh2_bytes", "egr_wstream_image_bytes",
-                        "egr_linear_wstream_workspace_bytes"):
+                        "egr_linear_wstream_workspace_bytes", "egr_rig_refine_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     return lib
 
@@ -1726,6 +1730,74 @@ def skeleton_resize(pose: torch.Tensor, valid: torch.Tensor, bone_length: torch.
             B, J,
             _p(out), _stream(), nbytes=B * J * 29.0)
     return out
+
+
+RIG_MAX_ITERATIONS = 256
+
+
+def _rig_fixed(what: str, fixed, V: int):
+    """The held cameras as a list of V flags (host memory: they travel to the kernel by value); None holds view 0 alone."""
+    if fixed is None:
+        return [v == 0 for v in range(V)]
+    if isinstance(fixed, torch.Tensor):
+        if fixed.dim() != 1 or fixed.dtype.is_floating_point or fixed.device.type == "meta":
+            raise ValueError(f"egorear_amd.{what}: fixed must be a sequence of {V} flags or a ({V},) bool tensor with data")
+        fixed = fixed.tolist()
+    try:
+        flags = [bool(f) for f in fixed]
+        exact = all(isinstance(f, (bool, int)) and f in (0, 1) for f in fixed)
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.{what}: fixed must be a sequence of {V} flags, got {fixed!r}") from None
+    if not exact or len(flags) != V:
+        raise ValueError(f"egorear_amd.{what}: fixed must be {V} flags, one a view, got {fixed!r}")
+    return flags
+
+
+def _rig_operands(coords, conf, cams, ctm, fixed, sx, sy, min_det_ratio, prior_weight, iterations, what: str, dense: bool = True):
+    """(B, V, J, the held cameras, per-frame matrices?) of a rig refinement; every shape / dtype / parameter error as ValueError.
+    coord_trans_mat may be (B, V, 4, 4) or (1, V, 4, 4), one rig for the clip."""
+    if coords.dim() != 4 or coords.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.{what}: coords must be (B, V, J, 2), got {tuple(coords.shape)}")
+    B, V = int(coords.shape[0]), int(coords.shape[1])
+    per_frame = 1
+    if ctm is not None and ctm.dim() == 4 and B > 1 and tuple(ctm.shape) == (1, V, 4, 4):
+        per_frame = 0
+    B, V, J = _tri_operands(coords, conf, cams, None if not per_frame else ctm, sx, sy, min_det_ratio, what, dense=dense)
+    if not per_frame:
+        _float32(what, (ctm, "coord_trans_mat"))
+        _contiguous(what, dense, (ctm, "coord_trans_mat"))
+    if B * J >= 1 << 28:
+        raise ValueError(f"egorear_amd.{what}: B * J must stay below 2^28, got {tuple(coords.shape)}")
+    flags = _rig_fixed(what, fixed, V)
+    _non_negative(what, "prior_weight", prior_weight)
+    if not _int_in(iterations, 1, RIG_MAX_ITERATIONS):
+        raise ValueError(f"egorear_amd.{what}: iterations must be an integer in 1..{RIG_MAX_ITERATIONS}, got {iterations!r}")
+    return B, V, J, flags, per_frame
+
+
+def rig_refine(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None, fixed=None, sx: float = 1.0,
+               sy: float = 1.0, threshold: float = 0.5, min_det_ratio: float = 1e-6, prior_weight: float = 0.0, iterations: int = 8):
+    """coords (B,V,J,2), conf (B,V,J), cams (V,30), ctm (B,V,4,4) | (1,V,4,4) | None as for triangulate; fixed: V host flags (None:
+    view 0) -> rotation (V,3) rad, matrix (V,3,3), ctm_out (B,V,4,4), cost0 (1), cost (1), pairs (1) i32, steps (1) i32, grad (1),
+    valid (1) u8: egr_rig_refine_f32, the rotations of the free cameras about their own centres that minimise the rays' distances over
+    the clip (include/egorear_hip.h states the objective and the solver).  The fp64 workspace is allocated here, like the outputs."""
+    B, V, J, flags, per_frame = _rig_operands(coords, conf, cams, ctm, fixed, sx, sy, min_det_ratio, prior_weight, iterations, "rig_refine")
+    _on_device("rig_refine", coords, conf, cams, ctm)
+    dev = coords.device
+    nbytes_ws = int(lib.egr_rig_refine_workspace_bytes(B, V, J))
+    ws = torch.empty((nbytes_ws // 8,), device=dev, dtype=torch.float64)
+    rotation = torch.empty((V, 3), device=dev, dtype=torch.float32)
+    matrix = torch.empty((V, 3, 3), device=dev, dtype=torch.float32)
+    ctm_out = torch.empty((B, V, 4, 4), device=dev, dtype=torch.float32)
+    cost0, cost, grad = (torch.empty((1,), device=dev, dtype=torch.float32) for _ in range(3))
+    pairs, steps = (torch.empty((1,), device=dev, dtype=torch.int32) for _ in range(2))
+    valid = torch.empty((1,), device=dev, dtype=torch.uint8)
+    mask = sum(1 << v for v, f in enumerate(flags) if f)
+    _launch("egr_rig_refine_f32", lib.egr_rig_refine_f32, _p(coords), _p(conf), _p(cams), _p(ctm), per_frame, B, V, J, float(sx), float(sy),
+            float(threshold), float(min_det_ratio), mask, float(prior_weight), int(iterations), _p(ws, torch.float64), nbytes_ws, _p(rotation),
+            _p(matrix), _p(ctm_out), _p(cost0), _p(cost), _p(pairs, torch.int32), _p(steps, torch.int32), _p(grad), _p(valid, torch.uint8),
+            _stream(), nbytes=B * J * V * (12.0 + 32.0 * (iterations + 2)) + B * V * 64.0)
+    return rotation, matrix, ctm_out, cost0, cost, pairs, steps, grad, valid
 
 
 TRAJECTORY_MAX_T = 4096           # frames of one clip of egr_trajectory.hip

@@ -654,6 +654,41 @@ int egr_trajectory_smooth_bwd_f32(const float* pose, const float* weight /* null
                                   float accel_weight, double* workspace /* 8 x T x N x J */, float* g_pose /* N x T x J x 3 */,
                                   float* g_weight /* N x T x J, nullable */, void* stream);
 
+/* Rig self-calibration: the cameras' rotations refined from the decoded 2-D joints of a clip.  Over the pairs
+ * (frame b, joint j), with the rays, weights and extrinsics of egr_triangulate_f32 (the same views used or excluded, w = conf),
+ *   E(dR_0..dR_{V-1}) = sum_pairs min_p sum_v w_v |P(dR_v^T d_v) (R_v p + t_v)|^2 + prior_weight sum_v |dR_v - I|_F^2,  P(d) = I - d d^T,
+ * dR_v a rotation of camera v about its own centre: p_cam' = dR_v (R_v p + t_v), M'_v = [dR_v 0; 0 1] M_v.  Translations are not
+ * refined: a ray-distance cost with free translations collapses the rig.  ctm: NULL (the syn rig), or (B, V, 4, 4) with
+ * ctm_per_frame != 0, or (1, V, 4, 4) for the clip with ctm_per_frame == 0.  fixed_mask: bit v holds camera v at dR = I (every bit
+ * set is legal: the result is the identity and cost == cost0).
+ *   A pair counts - decided once, at dR = I - when two views or more carry weight and its 3 x 3 normal equations pass
+ *   egr_triangulate_f32's test with min_det_ratio.  Later iterates solve the same pairs with the positivity test alone; a candidate at
+ *   which a counted pair fails is refused like one that raises E.
+ *   Solver: Levenberg-Marquardt on the Gauss-Newton model, the point of every pair eliminated by its 3 x 3 Schur complement, the local
+ *   update dR_v <- exp([delta_v]x) dR_v, the prior's gradient and exact Hessian at delta = 0 added.  mu starts at 1e-4; every
+ *   iteration solves (H + mu diag H) delta = -g over the free cameras at the accepted rotations (LDL^T), evaluates the candidate, and
+ *   keeps it iff every counted pair factors and E falls strictly - mu then times 0.1 (not below 1e-12); a refused one multiplies mu by
+ *   10 (not above 1e12) and the next iteration solves again from the stored system.  `iterations` (1..256) candidates are tried,
+ *   always: 1 + 2 (iterations + 1) launches on `stream`, all solver state in `workspace`, no host synchronisation.
+ * rotation (V, 3): the rotation vectors of dR, rad; matrix (V, 3, 3): dR; ctm_out (B, V, 4, 4): [matrix 0; 0 1] M in the decoders'
+ * convention (translations in m) - for the syn rig M is diag(f, f, 1) with f = -1 for a flipped camera and the record's offset * 0.01
+ * as fp32 - the product of the fp32 matrices formed in fp64 and rounded once; cost0, cost (1 each): sum w dist^2 / sum w over the counted pairs before and after, cm^2
+ * (egr_triangulate_f32's cost, pooled); pairs (1): the counted pairs; steps (1): the kept candidates; grad (1): the largest |dE/d delta|
+ * component over the free cameras at the result; valid (1): 0 when no pair counts, the start is not finite or its undamped system does
+ * not factor (a pivot at or below 1e-10 of its diagonal entry) - then every rotation is the identity, ctm_out is M and the scalars are 0.
+ * workspace: egr_rig_refine_workspace_bytes(B, V, J) bytes (0 for shapes the entry refuses), contents unspecified before and after.
+ * One thread per pair and iteration, the 94 sums of a pair reduced in a fixed order - an xor butterfly of wave shuffles, the waves of a
+ * workgroup in LDS in wave order, one record a workgroup, the records in block order by the one workgroup of the step kernel: no
+ * atomics, the same bits every run whatever the grid's scheduling.  fp64 arithmetic on fp32 operands.
+ * EGR_EINVAL: the shapes egr_triangulate_f32 refuses, B * J >= 2^28, fixed_mask outside 0..2^V - 1, prior_weight negative or not
+ * finite, iterations outside 1..256; EGR_EWORKSPACE: workspace_bytes too small. */
+int64_t egr_rig_refine_workspace_bytes(int32_t B, int32_t V, int32_t J);
+int egr_rig_refine_f32(const float* coords, const float* conf, const float* cams, const float* ctm /* nullable */, int32_t ctm_per_frame,
+                       int32_t B, int32_t V, int32_t J, float sx, float sy, float threshold, float min_det_ratio, int32_t fixed_mask,
+                       float prior_weight, int32_t iterations, double* workspace, int64_t workspace_bytes, float* rotation /* V x 3 */,
+                       float* matrix /* V x 3 x 3 */, float* ctm_out /* B x V x 4 x 4 */, float* cost0, float* cost, int32_t* pairs,
+                       int32_t* steps, float* grad, uint8_t* valid, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
