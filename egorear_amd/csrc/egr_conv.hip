@@ -30,8 +30,7 @@
 
 #include <cstdlib>
 
-#include "egr_conv_shared.h"
-#include "egr_up2.h"
+#include "egr_conv_epi.h"
 
 using namespace egrc;
 
@@ -117,7 +116,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
     if constexpr (X6 && NPL == 2) act_prescale(a.amax_in, lane, sa, ads);
     const float* const wdsg = (X6 && NPL == 2) ? a.wds + grp * d.gp : nullptr;
     float amx = 0.f;
-    auto track4 = [&](const f32x4& v) { amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3]))); };
 
     // XCD-aware tile order: blocks b and b+8 share an L2; hand each XCD a contiguous run of tiles,
     // with the N tiles of one M tile adjacent so the activation tile is fetched into one L2 only.
@@ -154,7 +152,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
     const int pseg = lane & 7;
     int* const tab0 = reinterpret_cast<int*>(lds + P::ROWOFF);   // table `slot`: [yoff | roff | xoff | mask | lx | ly] x BM
     const unsigned fullmask = (d.kh * d.kw >= 32) ? 0xffffffffu : ((1u << (d.kh * d.kw)) - 1u);
-    auto decode = [&](int tm_, int slot) {
+    auto decode = [&](int tm_, int slot, bool next_tile) {
     int* const s_yoff = tab0 + slot * P::TCOLS * BM;
     int* const s_roff = s_yoff + BM;
     int* const s_xoff = s_roff + BM;
@@ -164,14 +162,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         int xo = 0, yo = -1, ro = 0;
         unsigned mk = 0u;
         if (m < a.M) {
-            // (n, ho, wo) of output pixel m: shifts when the geometry is a power of two, multiply-high otherwise
             int n, pix, ho, wo;
-            if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-            else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-            if (a.wo_shift >= 0) { ho = pix >> a.wo_shift; wo = pix & (Wenum - 1); }
-            else { ho = fdiv(pix, a.dWo); wo = pix - ho * Wenum; }
+            pixel_of(a, m, HoWo, n, pix);
+            row_of(a, pix, Wenum, ho, wo);
             if (a.cls_mode) { ho = 2 * ho + ph; wo = 2 * wo + pw; pix = ho * d.wo + wo; }
-            const int xbase = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+            const int xbase = image_offset(d.xmap, a.x_plain, a.dXin, n);
             if (!d.transposed) {
                 const int hi0 = ho * d.stride - d.pad, wi0 = wo * d.stride - d.pad;
                 // 32-bit element offsets (the host bounds every operand below 2^31 elements); may be negative for halo rows
@@ -204,21 +199,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                 }
             }
             mk &= fullmask;
-            yo = (a.y_plain ? n * (int)d.ymap.stride_inner : (int)fmap(d.ymap, a.dYin, n)) + (d.out_nchw ? pix : pix * d.ldy);
-            if (d.res_mode == EGR_RES_BEFORE_ACT || d.res_mode == EGR_RES_AFTER_ACT) ro = (a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + pix * d.ldr;
+            yo = image_offset(d.ymap, a.y_plain, a.dYin, n) + (d.out_nchw ? pix : pix * d.ldy);
+            if (d.res_mode == EGR_RES_BEFORE_ACT || d.res_mode == EGR_RES_AFTER_ACT) ro = image_offset(d.rmap, a.r_plain, a.dRin, n) + pix * d.ldr;
             if (d.res_mode == EGR_RES_UP2_BEFORE_ACT) {
-                // residual = bilinear x2 upsampling (align_corners=True, ATen arithmetic as in upsample2x_kernel) of a HALF-resolution
-                // tensor: offset of the upper-left neighbour, the two weights; sign bit set = the right / lower neighbour is the
-                // same pixel (last column / row)
-                const int hl = d.ho >> 1, wl = d.wo >> 1;
-                const float shh = (d.ho > 1) ? (float)(hl - 1) / (float)(d.ho - 1) : 0.f;
-                const float sww = (d.wo > 1) ? (float)(wl - 1) / (float)(d.wo - 1) : 0.f;
-                const float fy = shh * (float)ho, fx = sww * (float)wo;
-                const int y0 = (int)fy, x0 = (int)fx;
-                const float ly1 = fminf(fmaxf(fy - (float)y0, 0.f), 1.f), lx1 = fminf(fmaxf(fx - (float)x0, 0.f), 1.f);
-                ro = (a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + (y0 * wl + x0) * d.ldr;
-                s_yoff[P::COL_LX * BM + r] = (int)(__float_as_uint(lx1) | (x0 + 1 > wl - 1 ? 0x80000000u : 0u));
-                s_yoff[P::COL_LY * BM + r] = (int)(__float_as_uint(ly1) | (y0 + 1 > hl - 1 ? 0x80000000u : 0u));
+                // up2_res, one word per axis: the weight, sign bit set = the right / lower neighbour is the same pixel
+                const Up2Res u = up2_res(d, ho, wo, next_tile);    // (next_tile: egrc::axis_rounded_product, the bits these rows always had)
+                ro = image_offset(d.rmap, a.r_plain, a.dRin, n) + u.off;
+                s_yoff[P::COL_LX * BM + r] = (int)(__float_as_uint(u.lx1) | (u.last_x ? 0x80000000u : 0u));
+                s_yoff[P::COL_LY * BM + r] = (int)(__float_as_uint(u.ly1) | (u.last_y ? 0x80000000u : 0u));
             }
         } else if (d.res_mode == EGR_RES_UP2_BEFORE_ACT) {
             s_yoff[P::COL_LX * BM + r] = 0;
@@ -232,7 +220,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         s_roff[r] = ro;
     }
     };
-    decode(tm, 0);
+    decode(tm, 0, false);
     int* s_yoff = tab0;
     int* s_roff = s_yoff + BM;
     int* s_xoff = s_roff + BM;
@@ -376,6 +364,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                 }
                 for (; sp < d.split_k; ++sp) sum += __hip_atomic_load(p0 + (int64_t)sp * slab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            // egrc::epi_value and the row mask, written out (as one call the persistent kernels spill more scalar registers)
             float v = sum * (scg ? scg[co] : 1.f) + (shg ? shg[co] : 0.f) * (rsg ? rsg[m] : 1.f);
             if (d.res_mode == EGR_RES_BEFORE_ACT) v += resg[(int64_t)s_roff[row] + co];
             v = egr_act(v, d.act);
@@ -397,6 +386,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                 int yo = s_yoff[row];
                 if (yo < 0) continue;
                 int m = tm * BM + row;
+                // egrc::epi_value and the row mask, written out (as one call the persistent kernels spill more scalar registers)
                 float v = sC[row * P::CS + c] * sc + sh * (rsg ? rsg[m] : 1.f);
                 if (d.res_mode == EGR_RES_BEFORE_ACT) v += resg[(int64_t)s_roff[row] + co];
                 v = egr_act(v, d.act);
@@ -446,19 +436,21 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
             f32x4 v = *reinterpret_cast<const f32x4*>(&sC[row * P::CS + cq * 4]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
+                // egrc::up2_res_add in front of the activation, its contractions still the compiler's here (they come out as the shared
+                // statement writes them): with the explicit form conv_igemm_x6_kernel<128, 64, .., 2> spills four registers
                 float t = v[e] * sc[e] + sh[e];
                 t += ly0 * (lx0 * v00[e] + lx1 * v01[e]) + ly1 * (lx0 * v10[e] + lx1 * v11[e]);
                 v[e] = (d.act == EGR_ACT_RELU) ? (t > 0.f ? t : 0.f) : t;
             }
             if (yo >= 0) {
                 *reinterpret_cast<f32x4*>(yg + (int64_t)yo + co) = v;
-                track4(v);
+                amax4(amx, v);
             }
         }
         return;
     }
 
-    if (a.mask) {  // dx = (acc [+ res]) * [mask > 0]  (the host guarantees the 16-byte path, no scale/shift/activation)
+    if (a.mask) {  // dx = (acc [+ res]) * [mask > 0]  (the host guarantees the 16-byte path, no scale/shift/activation: not epi_value)
         const float* const maskg = a.mask + grp * d.gy;
 #pragma unroll
         for (int it = 0; it < BM / RPI; ++it) {
@@ -476,7 +468,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = mk[e] > 0.f ? v[e] : 0.f;
-            track4(v);
+            amax4(amx, v);
             *reinterpret_cast<f32x4*>(yg + (int64_t)yo + co) = v;
         }
         return;
@@ -499,13 +491,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                 f32x4 v = *reinterpret_cast<const f32x4*>(&sC[row * P::CS + cq * 4]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[e] = v[e] * sc[e] + sh[e];
-                    ds[e] += (double)v[e];
-                    dq[e] += (double)v[e] * (double)v[e];
-                    lo[e] = fminf(lo[e], v[e]);
-                    hi[e] = fmaxf(hi[e], v[e]);
+                    v[e] = epi_value(v[e], sc[e], sh[e], 1.f, 0.f, EGR_ACT_NONE, EGR_RES_NONE);
+                    bn_accumulate(v[e], ds[e], dq[e], lo[e], hi[e]);
                 }
-                track4(v);
+                amax4(amx, v);
                 *reinterpret_cast<f32x4*>(yg + (int64_t)yo + co) = v;
             }
             __syncthreads();                               // the staged tile has been read by everybody: its words are free
@@ -538,15 +527,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                         lo[e] = fminf(lo[e], rf[(k * QPR + cq) * 8 + e]);
                         hi[e] = fmaxf(hi[e], rf[(k * QPR + cq) * 8 + 4 + e]);
                     }
-                const int64_t slab = ((int64_t)grp * a.tilesM + tm) * 2 * d.cout + co;
-                float* const mm = reinterpret_cast<float*>(a.bn_part + (int64_t)d.groups * a.tilesM * 2 * d.cout);   // the extremes sit behind the sums
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    a.bn_part[slab + e] = ds[e];
-                    a.bn_part[slab + d.cout + e] = dq[e];
-                    mm[slab + e] = lo[e];
-                    mm[slab + d.cout + e] = hi[e];
-                }
+                for (int e = 0; e < 4; ++e) bn_store(a, grp, tm, co + e, ds[e], dq[e], lo[e], hi[e]);
             }
             __syncthreads();                               // (persistent launches stage the next tile into the same words)
             return;
@@ -566,15 +548,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
                     else rr = *reinterpret_cast<const f32x4*>(resg + (int64_t)s_roff[row] + co);
                 }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float t = v[e] * sc[e] + sh[e];
-                    if constexpr (RES == EGR_RES_BEFORE_ACT) t += rr[e];
-                    if constexpr (ACT == EGR_ACT_RELU) t = t > 0.f ? t : 0.f;
-                    if constexpr (ACT == EGR_ACT_GELU) t = 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f));
-                    if constexpr (RES == EGR_RES_AFTER_ACT) t += rr[e];
-                    v[e] = t;
-                }
-                track4(v);
+                for (int e = 0; e < 4; ++e) v[e] = epi_value(v[e], sc[e], sh[e], 1.f, rr[e], ACT, RES);
+                amax4(amx, v);
 #ifdef X6_EXP_NOSTORE
                 if (v[0] == 12345.678f)
 #endif
@@ -620,10 +595,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float t = v[e] * sc[e] + sh[e] * rs;
-            if (d.res_mode == EGR_RES_BEFORE_ACT) t += rr[e];
-            t = egr_act(t, d.act);
-            if (d.res_mode == EGR_RES_AFTER_ACT) t += rr[e];
+            const float t = epi_value(v[e], sc[e], sh[e], rs, rr[e], d.act, d.res_mode);
             v[e] = keep ? t : 0.f;
             if (co + e < d.cout) amx = fmaxf(amx, fabsf(v[e]));
         }
@@ -658,10 +630,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         const int HPI = (RTI + 1) * WP, HP = NI * HPI, PPI = RTI * wo;
         const int m0 = tm * BM;
         int n0, pix0;
-        if (a.howo_shift >= 0) { n0 = m0 >> a.howo_shift; pix0 = m0 & (HoWo - 1); }
-        else { n0 = fdiv(m0, a.dHoWo); pix0 = m0 - n0 * HoWo; }
-        const int y0 = (a.wo_shift >= 0) ? (pix0 >> a.wo_shift) : fdiv(pix0, a.dWo);
-        const int xbase = a.x_plain ? n0 * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n0);
+        pixel_of(a, m0, HoWo, n0, pix0);
+        const int y0 = row_index(a, pix0);
+        const int xbase = image_offset(d.xmap, a.x_plain, a.dXin, n0);
         const int abias = (d.w + 1) * d.ldx * 4;
         const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
             uniform_ptr(reinterpret_cast<const char*>(xg) - abias), 0, 0x80000000u, 0x00020000);
@@ -675,7 +646,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
             const int u = tid + NT * i, hp = u >> 2, seg = u & 3;
             const int il = hp / HPI, hq = hp - il * HPI;
             const int pr = hq / WP, pc = hq - pr * WP;
-            const int ioff = (il == 0) ? 0 : ((a.x_plain ? (n0 + il) * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n0 + il)) - xbase);
+            const int ioff = (il == 0) ? 0 : (image_offset(d.xmap, a.x_plain, a.dXin, n0 + il) - xbase);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int dy = 2 * pr - (q >> 1), ix = 2 * pc - (q & 1);
@@ -862,10 +833,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         // the tile's first image and row (wave-uniform)
         const int m0 = tm * BM;
         int n0, pix0;
-        if (a.howo_shift >= 0) { n0 = m0 >> a.howo_shift; pix0 = m0 & (HoWo - 1); }
-        else { n0 = fdiv(m0, a.dHoWo); pix0 = m0 - n0 * HoWo; }
-        const int y0 = (a.wo_shift >= 0) ? (pix0 >> a.wo_shift) : fdiv(pix0, a.dWo);
-        const int xbase = a.x_plain ? n0 * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n0);
+        pixel_of(a, m0, HoWo, n0, pix0);
+        const int y0 = row_index(a, pix0);
+        const int xbase = image_offset(d.xmap, a.x_plain, a.dXin, n0);
         const int abias = (d.w + 1) * d.ldx * 4;                 // the window starts one row + one pixel early: halo offsets >= 0
         const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
             uniform_ptr(reinterpret_cast<const char*>(xg) - abias), 0, 0x80000000u, 0x00020000);
@@ -879,7 +849,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
             const int il = hp / HPI, hq = hp - il * HPI;
             const int hr = hq / WP, hc = hq - hr * WP;
             const bool ok = hp < HP && (unsigned)(y0 + hr - 1) < (unsigned)d.h && (unsigned)(hc - 1) < (unsigned)d.w;
-            const int ioff = (il == 0) ? 0 : ((a.x_plain ? (n0 + il) * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n0 + il)) - xbase);
+            const int ioff = (il == 0) ? 0 : (image_offset(d.xmap, a.x_plain, a.dXin, n0 + il) - xbase);
             hvo[i] = ok ? (ioff + ((hr - 1) * d.w + (hc - 1)) * d.ldx) * 4 + seg * 16 + abias : (int)0x80000000;
         }
         int abase[FM], bvo[FN];
@@ -1397,7 +1367,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
             int tmn = 0, tnn = 0;
             if (more) {
                 tile_of(vn, tmn, tnn);
-                decode(tmn, slot ^ 1);
+                decode(tmn, slot ^ 1, true);
             }
             const int* const t_yoff = tab0 + slot * P::TCOLS * BM;
             epilogue(tm, tn, t_yoff, t_yoff + BM, [&] {
@@ -1483,6 +1453,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvArgs a) {
         const int m = mm[e], co = cc[e];
         const float s = ss[e];
         int n = m / HoWo, pix = m - n * HoWo;
+        // egrc::epi_value and the row mask, written out: through the shared statement the products here are rounded apart, not fused
         float sc = scg ? scg[co] : 1.f;
         float sh = shg ? shg[co] : 0.f;
         float rs = rsg ? rsg[m] : 1.f;
@@ -1614,6 +1585,7 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const ConvArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (co + e < d.cout) {
+                // egrc::epi_value and the row mask, written out (as in splitk_reduce_kernel: the fused product would come apart)
                 float t = v[e] * (scg ? scg[co + e] : 1.f) + (shg ? shg[co + e] : 0.f) * rs;
                 if (d.res_mode == EGR_RES_BEFORE_ACT) t += rp[e];
                 t = egr_act(t, d.act);
@@ -1713,7 +1685,6 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(masked ? a.mask + grp * d.gy : a.x), 0, 0x80000000u, 0x00020000);
     const int HoWo = d.ho * d.wo;
-    constexpr int OOB = (int)0x80000000;
     const int T = (a.M + 31) >> 5, NW = gridDim.x * 8;
     int t = blockIdx.x * 8 + wave;
 
@@ -1721,12 +1692,12 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
     auto x_off = [&](int tile) {
         const int m = tile * 32 + p;
         int n, pix;
-        if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-        else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-        const int xb = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+        pixel_of(a, m, HoWo, n, pix);
+        const int xb = image_offset(d.xmap, a.x_plain, a.dXin, n);
         int ipix = pix;
         if (d.stride == 2) {             // 1x1 / stride 2 (the residual blocks' down-sampling convs): input pixel (2 ho, 2 wo)
-            const int ho = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), wo = pix - ho * d.wo;
+            int ho, wo;
+            row_of(a, pix, d.wo, ho, wo);
             ipix = 2 * ho * d.w + 2 * wo;
         }
         return (tile < T && m < a.M) ? (xb + ipix * d.ldx) * 4 + h * 16 : OOB;
@@ -1737,13 +1708,12 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
     const float up_sh = UP2 ? egr_up2::scale(hs, d.h) : 0.f, up_sw = UP2 ? egr_up2::scale(ws, d.w) : 0.f;
     auto up_src_off = [&](int tile, int (&so)[UPL]) {
         const int m0 = tile * 32;
-        int n, pix;
-        if (a.howo_shift >= 0) { n = m0 >> a.howo_shift; pix = m0 & (HoWo - 1); }
-        else { n = fdiv(m0, a.dHoWo); pix = m0 - n * HoWo; }
-        const int oy = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), ox0 = pix - oy * d.wo;
+        int n, pix, oy, ox0;
+        pixel_of(a, m0, HoWo, n, pix);
+        row_of(a, pix, d.wo, oy, ox0);
         const egr_up2::Axis ay = egr_up2::axis(up_sh, oy, hs);
         const int sx0 = egr_up2::first_index(up_sw, ox0);
-        const int xb = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+        const int xb = image_offset(d.xmap, a.x_plain, a.dXin, n);
 #pragma unroll
         for (int i = 0; i < UPL; ++i) {
             const int e = lane + 64 * i, s = e >> 3, r = s >= UPW ? 1 : 0, c = s - UPW * r;
@@ -1814,10 +1784,9 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
             if constexpr (UP2) {
                 up_src_off(t + NW, so_n);
                 const int m = t * 32 + p;
-                int n, pix;
-                if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-                else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-                const int oy = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), ox = pix - oy * d.wo;
+                int n, pix, oy, ox;
+                pixel_of(a, m, HoWo, n, pix);
+                row_of(a, pix, d.wo, oy, ox);
                 const egr_up2::Axis ay = egr_up2::axis(up_sh, oy, hs), ax = egr_up2::axis(up_sw, ox, ws);
                 const int sx0 = egr_up2::first_index(up_sw, ox - p);        // (the tile starts at column ox - p of the same row)
                 uy0 = ay.l0; uy1 = ay.l1; ux0 = ax.l0; ux1 = ax.l1;
@@ -1928,45 +1897,12 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
             // through a wave-private 32 x 32 LDS patch (rows padded to 144 bytes; no barrier - one wave's LDS operations execute in
             // order) and comes back row-major: lane = (row i*8 + lane/8, channel quad lane%8), an instruction writes 8 whole 128-byte lines.
             const int m = t * 32 + p;
-            int n, pix;
-            if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-            else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-            const bool live = m < a.M;
-            const int yo_p = live ? ((a.y_plain ? n * (int)d.ymap.stride_inner : (int)fmap(d.ymap, a.dYin, n)) + pix * d.ldy + tn * NCF * 32) * 4 : OOB;
-            int ro_p = OOB, ox_p = 0, oy_p = 0;
-            float lx1_p = 0.f, ly1_p = 0.f;
-            if constexpr (RESK == 1) {
-                if (live) ro_p = ((a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + pix * d.ldr + tn * NCF * 32) * 4;
-            }
-            if constexpr (RESK == 2) {
-                // bilinear x2 (align_corners = True, ATen arithmetic as in upsample2x_kernel) of a half-resolution tensor
-                const int ho = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), wo = pix - ho * d.wo;
-                const int hl = d.ho >> 1, wl = d.wo >> 1;
-                const float shh = (d.ho > 1) ? (float)(hl - 1) / (float)(d.ho - 1) : 0.f;
-                const float sww = (d.wo > 1) ? (float)(wl - 1) / (float)(d.wo - 1) : 0.f;
-                const float fy = shh * (float)ho, fx = sww * (float)wo;
-                const int y0 = (int)fy, x0 = (int)fx;
-                // (fused multiply-subtract, as the compiler contracts the same expressions of the tiled kernels' row decode)
-                ly1_p = fminf(fmaxf(__builtin_fmaf(shh, (float)ho, -(float)y0), 0.f), 1.f);
-                lx1_p = fminf(fmaxf(__builtin_fmaf(sww, (float)wo, -(float)x0), 0.f), 1.f);
-                if (live) ro_p = ((a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + (y0 * wl + x0) * d.ldr + tn * NCF * 32) * 4;
-                ox_p = (x0 + 1 > wl - 1) ? 0 : d.ldr * 4;
-                oy_p = (y0 + 1 > hl - 1) ? 0 : wl * d.ldr * 4;
-            }
+            const PwRow own = pw_row_own<RESK>(a, m, m < a.M, HoWo, tn * NCF * 32);
             // the four rows this lane stores: their parameters come from the lanes that own those pixels
             const int qd = lane & 7, rsub = lane >> 3;
-            int yo[4], ro[4], ox[4], oy[4];
-            float lx1[4], ly1[4];
+            PwRow rw[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int src = i * 8 + rsub;
-                yo[i] = __shfl(yo_p, src) + qd * 16;
-                if constexpr (RESK != 0) ro[i] = __shfl(ro_p, src) + qd * 16;
-                if constexpr (RESK == 2) {
-                    ox[i] = __shfl(ox_p, src); oy[i] = __shfl(oy_p, src);
-                    lx1[i] = __shfl(lx1_p, src); ly1[i] = __shfl(ly1_p, src);
-                }
-            }
+            for (int i = 0; i < 4; ++i) rw[i] = pw_row_from<RESK>(own, i * 8 + rsub, qd);
             uint8_t* const patch = lds + WBYTES + NCF * 32 * 8 + wave * PATCH;
 #pragma unroll
             for (int cf = 0; cf < NCF; ++cf) {
@@ -1975,7 +1911,7 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
                     if (masked) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            mk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, yo[i] + cf * 128, 0, 0));
+                            mk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, rw[i].yo + cf * 128, 0, 0));
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) mk[i] = f32x4{1.f, 1.f, 1.f, 1.f};
@@ -1984,11 +1920,12 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
                 if constexpr (RESK != 0) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        r00[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[i] + cf * 128, 0, 0));
+                        const PwRow& w = rw[i];
+                        r00[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + cf * 128, 0, 0));
                         if constexpr (RESK == 2) {
-                            r01[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[i] + ox[i] + cf * 128, 0, 0));
-                            r10[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[i] + oy[i] + cf * 128, 0, 0));
-                            r11[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[i] + oy[i] + ox[i] + cf * 128, 0, 0));
+                            r01[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.ox + cf * 128, 0, 0));
+                            r10[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.oy + cf * 128, 0, 0));
+                            r11[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.oy + w.ox + cf * 128, 0, 0));
                         }
                     }
                 }
@@ -2005,22 +1942,15 @@ __device__ __forceinline__ void conv_pw_x6_body(const ConvArgs& a) {
                     f32x4 v = *reinterpret_cast<const f32x4*>(patch + (i * 8 + rsub) * 144 + qd * 16);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float tt = v[e] * sc[e] + sh[e];
-                        if constexpr (RESK == 1) tt += res_before ? r00[i][e] : 0.f;
-                        if constexpr (RESK == 2) {
-                            const float lx0 = 1.f - lx1[i], ly0 = 1.f - ly1[i];
-                            tt += ly0 * (lx0 * r00[i][e] + lx1[i] * r01[i][e]) + ly1[i] * (lx0 * r10[i][e] + lx1[i] * r11[i][e]);
-                        }
-                        tt = tt > floor_ ? tt : floor_;
-                        if constexpr (RESK == 1) tt += res_before ? 0.f : r00[i][e];
+                        float tt = pw_value<RESK>(v[e], sc[e], sh[e], r00[i][e], r01[i][e], r10[i][e], r11[i][e], rw[i].lx1, rw[i].ly1, res_before, floor_);
                         if constexpr (RESK != 2) tt = mk[i][e] > 0.f ? tt : 0.f;
                         v[e] = tt;
                     }
-                    if (cok && yo[i] >= 0) amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                    if (cok && rw[i].yo >= 0) amax4(amx, v);
 #ifdef PW_EXP_NOSTORE
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, (v[0] == 12345.678f) ? yo[i] + cf * 128 : OOB, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, (v[0] == 12345.678f) ? rw[i].yo + cf * 128 : OOB, 0, 0);
 #else
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, cok ? yo[i] + cf * 128 : OOB, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, cok ? rw[i].yo + cf * 128 : OOB, 0, 0);
 #endif
                 }
                 __builtin_amdgcn_wave_barrier();

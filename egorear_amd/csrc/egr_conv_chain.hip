@@ -23,7 +23,7 @@
 // first product's registers are dead, and have the whole epilogue to land.
 // LDS: W1 (cin 64: 32 KB, 128: 64 KB) + W2 (64 KB) + the channel vectors + one 16-row epilogue patch per wave (rows come back as whole
 // 128-byte lines, as in conv_pw_x6_kernel; 16 rows instead of 32 so that the 128 -> 128 -> 128 chain fits 160 KB).
-#include "egr_conv_shared.h"
+#include "egr_conv_epi.h"
 
 using namespace egrc;
 
@@ -46,8 +46,6 @@ struct ChainArgs {
     int64_t gw2, gp1;        // group strides: 16-bit elements of w2; floats of shift1 / W1's descale
     int act1;
 };
-
-constexpr int OOB = (int)0x80000000;
 
 // KS1 = cin / 16 (4 / 8); the intermediate and the output have 128 channels (four 32-row fragments each).
 // RESK: 0 no residual, 1 residual of the output's shape, 2 half-resolution residual up-sampled on the fly (EGR_RES_UP2_BEFORE_ACT)
@@ -88,9 +86,8 @@ __global__ __launch_bounds__(512) void conv_pw_chain_kernel(const ChainArgs ca) 
     auto x_off = [&](int tile) {      // byte offset of the lane's pixel in x (OOB past the last pixel: the loads return zeros)
         const int m = tile * 32 + p;
         int n, pix;
-        if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-        else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-        const int xb = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+        pixel_of(a, m, HoWo, n, pix);
+        const int xb = image_offset(d.xmap, a.x_plain, a.dXin, n);
         return (tile < T && m < a.M) ? (xb + pix * d.ldx) * 4 + h * 16 : OOB;
     };
     // weights -> LDS, both images, permuted to the lane's k order (lane half h holds k = {4h .. 4h+3} u {8+4h .. 8+4h+3} of a k16 step:
@@ -207,8 +204,7 @@ __global__ __launch_bounds__(512) void conv_pw_chain_kernel(const ChainArgs ca) 
                 const f32x4 sh = *reinterpret_cast<const f32x4*>(s_sh1 + cf * 32 + 8 * g + 4 * h);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float v = acc1[cf][4 * g + e] * sc[e] + sh[e];
-                    v = v > floor1 ? v : floor1;
+                    const float v = pw_value(acc1[cf][4 * g + e], sc[e], sh[e], floor1);
                     acc1[cf][4 * g + e] = v;
                     pmax = fmaxf(pmax, fabsf(v));
                 }
@@ -261,49 +257,17 @@ __global__ __launch_bounds__(512) void conv_pw_chain_kernel(const ChainArgs ca) 
         SB_G();
         // ---------------------------------------------------------------- epilogue (conv_pw_x6_kernel's, on 16-row patches)
         const int m = t * 32 + p;
-        int n, pix;
-        if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-        else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-        const bool live = m < a.M;
-        const int yo_p = live ? ((a.y_plain ? n * (int)d.ymap.stride_inner : (int)fmap(d.ymap, a.dYin, n)) + pix * d.ldy) * 4 : OOB;
-        int ro_p = OOB, ox_p = 0, oy_p = 0;
-        float lx1_p = 0.f, ly1_p = 0.f;
-        if constexpr (RESK == 1) {
-            if (live) ro_p = ((a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + pix * d.ldr) * 4;
-        }
-        if constexpr (RESK == 2) {
-            // bilinear x2 (align_corners = True, ATen arithmetic as in upsample2x_kernel) of a half-resolution tensor
-            const int ho = (a.wo_shift >= 0) ? (pix >> a.wo_shift) : fdiv(pix, a.dWo), wo = pix - ho * d.wo;
-            const int hl = d.ho >> 1, wl = d.wo >> 1;
-            const float shh = (d.ho > 1) ? (float)(hl - 1) / (float)(d.ho - 1) : 0.f;
-            const float sww = (d.wo > 1) ? (float)(wl - 1) / (float)(d.wo - 1) : 0.f;
-            const float fy = shh * (float)ho, fx = sww * (float)wo;
-            const int y0 = (int)fy, x0 = (int)fx;
-            ly1_p = fminf(fmaxf(__builtin_fmaf(shh, (float)ho, -(float)y0), 0.f), 1.f);
-            lx1_p = fminf(fmaxf(__builtin_fmaf(sww, (float)wo, -(float)x0), 0.f), 1.f);
-            if (live) ro_p = ((a.r_plain ? n * (int)d.rmap.stride_inner : (int)fmap(d.rmap, a.dRin, n)) + (y0 * wl + x0) * d.ldr) * 4;
-            ox_p = (x0 + 1 > wl - 1) ? 0 : d.ldr * 4;
-            oy_p = (y0 + 1 > hl - 1) ? 0 : wl * d.ldr * 4;
-        }
+        const PwRow own = pw_row_own<RESK>(a, m, m < a.M, HoWo, 0);
         const int qd = lane & 7, rsub = lane >> 3;
         uint8_t* const patch = lds + W1B + W2B + VEC + wave * PATCH;
         // Eight steps (pixel half hp = it / 4, fragment cf = it % 4).  The residual quads of step it + 1 are requested BEFORE step it's
         // stores: vector-memory operations retire in order, so a residual load issued behind the previous step's stores would wait for
         // those stores to be acknowledged as well (measured on the single launches: one exposed round trip per step, 15 us per tile).
-        int yo[2][2], ro[2][2], ox[2][2], oy[2][2];       // [hp][row i]: the two rows this lane stores in each half
-        float lx1[2][2], ly1[2][2];
+        PwRow rw[2][2];                                   // [hp][row i]: the two rows this lane stores in each half
 #pragma unroll
         for (int hp = 0; hp < 2; ++hp)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int src = hp * 16 + i * 8 + rsub;       // parameters come from the lane that owns that pixel
-                yo[hp][i] = __shfl(yo_p, src) + qd * 16;
-                if constexpr (RESK != 0) ro[hp][i] = __shfl(ro_p, src) + qd * 16;
-                if constexpr (RESK == 2) {
-                    ox[hp][i] = __shfl(ox_p, src); oy[hp][i] = __shfl(oy_p, src);
-                    lx1[hp][i] = __shfl(lx1_p, src); ly1[hp][i] = __shfl(ly1_p, src);
-                }
-            }
+            for (int i = 0; i < 2; ++i) rw[hp][i] = pw_row_from<RESK>(own, hp * 16 + i * 8 + rsub, qd);
         constexpr int NR = RESK == 2 ? 4 : (RESK == 1 ? 1 : 0);
         f32x4 rq[2][NR > 0 ? NR : 1];                        // [parity of the step][corner]
         // sixteen steps: (pixel half hp, fragment cf, row i of the two rows a lane stores per half)
@@ -315,12 +279,13 @@ __global__ __launch_bounds__(512) void conv_pw_chain_kernel(const ChainArgs ca) 
 #endif
                 // RESK == 1: the residual has the OUTPUT's shape - a fragment past cout (cout < 128) lies outside its row (and, at the
                 // last pixel, outside the tensor): not requested, like the stores of those channels
-                const int r0 = (RESK == 1 && cf * 32 + 4 * qd >= d.cout) ? OOB : ro[hp][i] + cf * 128;
+                const PwRow& w = rw[hp][i];
+                const int r0 = (RESK == 1 && cf * 32 + 4 * qd >= d.cout) ? OOB : w.ro + cf * 128;
                 rq[par][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, r0, 0, 0));
                 if constexpr (RESK == 2) {
-                    rq[par][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[hp][i] + ox[hp][i] + cf * 128, 0, 0));
-                    rq[par][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[hp][i] + oy[hp][i] + cf * 128, 0, 0));
-                    rq[par][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[hp][i] + oy[hp][i] + ox[hp][i] + cf * 128, 0, 0));
+                    rq[par][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.ox + cf * 128, 0, 0));
+                    rq[par][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.oy + cf * 128, 0, 0));
+                    rq[par][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, w.ro + w.oy + w.ox + cf * 128, 0, 0));
                 }
             }
         };
@@ -359,24 +324,15 @@ __global__ __launch_bounds__(512) void conv_pw_chain_kernel(const ChainArgs ca) 
                 const int st = 2 * u + i, par = st & 1;
                 if (st + 1 < 16) res_issue(st + 1, par ^ 1);
                 SB_E();
+                const PwRow& w = rw[hp][i];
                 f32x4 v = vv[i];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float tt = v[e] * sc[e] + sh[e];
-                    if constexpr (RESK == 1) tt += res_before ? rq[par][0][e] : 0.f;
-                    if constexpr (RESK == 2) {
-                        const float lx0 = 1.f - lx1[hp][i], ly0 = 1.f - ly1[hp][i];
-                        tt += ly0 * (lx0 * rq[par][0][e] + lx1[hp][i] * rq[par][1][e]) + ly1[hp][i] * (lx0 * rq[par][2][e] + lx1[hp][i] * rq[par][3][e]);
-                    }
-                    tt = tt > floor_ ? tt : floor_;
-                    if constexpr (RESK == 1) tt += res_before ? 0.f : rq[par][0][e];
-                    v[e] = tt;
-                }
-                if (cok && yo[hp][i] >= 0) amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                for (int e = 0; e < 4; ++e) v[e] = pw_value<RESK>(v[e], sc[e], sh[e], rq[par][0][e], rq[par][RESK == 2 ? 1 : 0][e], rq[par][RESK == 2 ? 2 : 0][e], rq[par][RESK == 2 ? 3 : 0][e], w.lx1, w.ly1, res_before, floor_);
+                if (cok && w.yo >= 0) amax4(amx, v);
 #ifdef CHAIN_EXP_NOSTORE
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, (v[0] == 12345.678f) ? yo[hp][i] + cf * 128 : OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, (v[0] == 12345.678f) ? w.yo + cf * 128 : OOB, 0, 0);
 #else
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, cok ? yo[hp][i] + cf * 128 : OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, cok ? w.yo + cf * 128 : OOB, 0, 0);
 #endif
                 SB_E();
             }
@@ -429,9 +385,8 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv_pw2_kernel(const Chain
     auto x_off = [&](int tile) {      // byte offset of the lane's pixel in x (OOB past the last pixel: the loads return zeros)
         const int m = tile * 32 + p;
         int n, pix;
-        if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-        else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
-        const int xb = a.x_plain ? n * (int)d.xmap.stride_inner : (int)fmap(d.xmap, a.dXin, n);
+        pixel_of(a, m, HoWo, n, pix);
+        const int xb = image_offset(d.xmap, a.x_plain, a.dXin, n);
         // (the first product takes its operands in the image's own k order - lane half h: k 8h .. 8h+7 of a k16 step - so a lane reads 32
         // CONTIGUOUS bytes of its pixel's row per step and the two lanes of a pixel share a 64-byte line: half the address work of the
         // {4h..4h+3} u {8+4h..} order that the register hand-over imposes on the second product only)
@@ -667,11 +622,11 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv_pw2_kernel(const Chain
         }
         // ---------------------------------------------------------------- epilogue (conv_pw_chain_kernel's, without a residual)
         const int m = t * 32 + p;
+        // (pw_row_own<0> / pw_row_from<0> written out: through the helpers the four-wave form's scratch grows from 32 to 56 bytes)
         int n, pix;
-        if (a.howo_shift >= 0) { n = m >> a.howo_shift; pix = m & (HoWo - 1); }
-        else { n = fdiv(m, a.dHoWo); pix = m - n * HoWo; }
+        pixel_of(a, m, HoWo, n, pix);
         const bool live = t < T && m < a.M;
-        const int yo_p = live ? ((a.y_plain ? n * (int)d.ymap.stride_inner : (int)fmap(d.ymap, a.dYin, n)) + pix * d.ldy) * 4 : OOB;
+        const int yo_p = live ? (image_offset(d.ymap, a.y_plain, a.dYin, n) + pix * d.ldy) * 4 : OOB;
         const int qd = lane & 7, rsub = lane >> 3;
         uint8_t* const patch = lds + R * CH + VEC + wave * PATCH;
         int yo[2][2];
@@ -706,12 +661,8 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv_pw2_kernel(const Chain
             for (int i = 0; i < 2; ++i) {
                 f32x4 v = vv[i];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float tt = v[e] * sc[e] + sh[e];
-                    tt = tt > floor_ ? tt : floor_;
-                    v[e] = tt;
-                }
-                if (cok && yo[hp][i] >= 0) amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                for (int e = 0; e < 4; ++e) v[e] = pw_value(v[e], sc[e], sh[e], floor_);
+                if (cok && yo[hp][i] >= 0) amax4(amx, v);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, cok ? yo[hp][i] + cf * 128 : OOB, 0, 0);
             }
         }

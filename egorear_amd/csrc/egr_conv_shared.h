@@ -1,5 +1,6 @@
-// Shared by the translation units of the implicit-GEMM convolution (egr_conv.hip, egr_conv_tapx.hip): launch arguments,
-// invariant-divisor helpers, the operand formats of the split kernels and their conversion / record helpers.
+// Shared by the translation units of the implicit-GEMM convolution (egr_conv.hip, egr_conv_tapx.hip, egr_conv_chain.hip): launch
+// arguments, invariant-divisor helpers, the operand formats of the split kernels and their conversion / record helpers.
+// (What the kernels' decodes and epilogues share sits on top of this file, in egr_conv_epi.h.)
 #pragma once
 #include <type_traits>
 #include <cstdlib>

@@ -23,7 +23,7 @@
 // Stride 2: the nine taps fall into four classes by the parity of the input pixel they read (see conv_igemm_tap2_kernel); the
 // four class planes of a chunk are staged together and the taps are unit shifts inside their class plane - the multiplying waves
 // run the same code with another tap table.
-#include "egr_conv_shared.h"
+#include "egr_conv_epi.h"
 
 using namespace egrc;
 
@@ -60,7 +60,6 @@ __device__ __forceinline__ void amax_flush_late(unsigned* amax_out, float amx, i
     if (ln == 0 && amx > 0.f)
         __hip_atomic_fetch_max(amax_out + (slot & 63), __float_as_uint(amx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-constexpr int XOOB = (int)0x80000000;   // buffer offset beyond every descriptor's range: loads return 0, stores are dropped
 
 // pixels of one 16-bit plane of a chunk
 //   stride 1: whole image rows ((BM / wo + 2) x (wo + 2)) or whole small images, wo in {8, 16, 32, 64}
@@ -141,7 +140,7 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
         T.tn = rem - T.tm * a.tilesN;
         const int m0 = T.tm * BM;
         int pix0;
-        T.n0 = m0 >> a.howo_shift;                            // (the host sends power-of-two image sizes only: shifts, no division)
+        T.n0 = m0 >> a.howo_shift;                            // egrc::pixel_of's shift branch, here and below (the host sends power-of-two image sizes only)
         pix0 = m0 & (HoWo - 1);
         T.y0 = PW ? 0 : pix0 >> a.wo_shift;
         T.xbase = (int)fmap(d.xmap, a.dXin, T.n0);
@@ -169,7 +168,7 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
             for (int i = 0; i < NUH; ++i) {
                 if constexpr (PW) {       // pixel p of the tile = output pixel tm BM + p, read at the same place; 16 units of 4 channels per pixel
                     const int u = lt + 256 * i, m = T.tm * BM + (u >> 4);
-                    const int n = m >> a.howo_shift, pix = m & (HoWo - 1);
+                    const int n = m >> a.howo_shift, pix = m & (HoWo - 1);      // (egrc::pixel_of's shift branch)
                     hvo[i] = ((int)fmap(d.xmap, a.dXin, n) + pix * d.ldx) * 4 + (u & 15) * 16;
                     continue;
                 }
@@ -181,7 +180,7 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
                 const int dy = STRIDE == 1 ? hr - 1 : 2 * hr - (q >> 1), ix = STRIDE == 1 ? hc - 1 : 2 * hc - (q & 1);
                 const bool ok = hp < HP && q < 4 && (unsigned)(STRIDE * T.y0 + dy) < (unsigned)d.h && (unsigned)ix < (unsigned)d.w;
                 const int ioff = (int)fmap(d.xmap, a.dXin, T.n0 + il) - T.xbase;
-                hvo[i] = ok ? (ioff + (dy * d.w + ix) * d.ldx) * 4 + seg * 16 + abias : XOOB;
+                hvo[i] = ok ? (ioff + (dy * d.w + ix) * d.ldx) * 4 + seg * 16 + abias : OOB;
             }
         };
         auto issue = [&](const int SET, int ck) __attribute__((always_inline)) {      // (SET: a literal at every call site)
@@ -269,9 +268,9 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
             const int sr = e * RPE + sr0;                                  // row of the staged (half) tile
             const int R = WHOLE ? sr : (sr >> 6) * 128 + H * 64 + (sr & 63);
             const int m = P.tm * BM + R;
-            const int n = m >> a.howo_shift, pix = m & (HoWo - 1);
-            yo = live ? ((int)fmap(d.ymap, a.dYin, n) + pix * d.ldy + co) * 4 : XOOB;
-            ro = (RES && live) ? ((int)fmap(d.rmap, a.dRin, n) + pix * d.ldr + co) * 4 : XOOB;
+            const int n = m >> a.howo_shift, pix = m & (HoWo - 1);         // egrc::pixel_of's shift branch (plan_tapx: power-of-two images only)
+            yo = live ? ((int)fmap(d.ymap, a.dYin, n) + pix * d.ldy + co) * 4 : OOB;
+            ro = (RES && live) ? ((int)fmap(d.rmap, a.dRin, n) + pix * d.ldr + co) * 4 : OOB;
         };
         auto res_load = [&](int H, int es) __attribute__((always_inline)) {      // residual quad of step es of half H
             int yo, ro;
@@ -286,20 +285,16 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
         auto finish = [&](f32x4 v, const f32x4& rr, const f32x4& mq, int yo) __attribute__((always_inline)) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
+                // egrc::epi_value on the descaled accumulator, written out: through the shared statement these kernels spill more
                 float t = (v[c] * dsq[c]) * sc[c] + sh[c];
                 if (RES && d.res_mode == EGR_RES_BEFORE_ACT) t += rr[c];
                 if (d.act == EGR_ACT_RELU) t = t > 0.f ? t : 0.f;
                 if (RES && d.res_mode == EGR_RES_AFTER_ACT) t += rr[c];
                 if (MASK) t = mq[c] > 0.f ? t : 0.f;
                 v[c] = t;
-                if constexpr (BNST) {
-                    bs[c] += (double)t;
-                    bq[c] += (double)t * (double)t;
-                    blo[c] = fminf(blo[c], t);
-                    bhi[c] = fmaxf(bhi[c], t);
-                }
+                if constexpr (BNST) bn_accumulate(t, bs[c], bq[c], blo[c], bhi[c]);
             }
-            if (live) amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            if (live) amax4(amx, v);
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, yo, 0, TAPX_ST_AUX);
         };
         // drain step K of the parked tile: K = 0, 1 out of the registers (first half), K = 2, 3 out of the staging area (second half);
@@ -368,15 +363,8 @@ __device__ __forceinline__ void conv_tapx_body(const ConvArgs& a) {
                             blo[c] = fminf(blo[c], red_f[(k * QPR + lt) * 8 + c]);
                             bhi[c] = fmaxf(bhi[c], red_f[(k * QPR + lt) * 8 + 4 + c]);
                         }
-                    const int64_t slab = ((int64_t)P.grp * a.tilesM + P.tm) * 2 * d.cout + co;
-                    float* const mm = reinterpret_cast<float*>(a.bn_part + (int64_t)d.groups * a.tilesM * 2 * d.cout);   // the extremes sit behind the sums
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        a.bn_part[slab + c] = bs[c];
-                        a.bn_part[slab + d.cout + c] = bq[c];
-                        mm[slab + c] = blo[c];
-                        mm[slab + d.cout + c] = bhi[c];
-                    }
+                    for (int c = 0; c < 4; ++c) bn_store(a, P.grp, P.tm, co + c, bs[c], bq[c], blo[c], bhi[c]);
                 }
                 stats_clear();
             }

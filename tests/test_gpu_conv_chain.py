@@ -56,6 +56,7 @@ CASES = [
     (1, 20, 12, 64, 124, 1, 1, 1, 1),        # ragged: 240 pixels (7.5 tiles), 124 output channels, residual before the ReLU
     (1, 8, 24, 128, 128, 1, 0, 1, 2),        # no activation between the convs, residual behind the second ReLU
     (5, 8, 8, 64, 128, 3, 1, 0, 0),          # three groups, 320 pixels each
+    (3, 12, 12, 64, 128, 1, 1, 1, 3),        # up-sampled residual on an image that is no power of two (the decode divides): 13.5 tiles
 ]
 
 

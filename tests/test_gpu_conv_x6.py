@@ -449,6 +449,8 @@ PW_CASES = [
     (5, 128, 128, 64, 192, 1, "plain"),            # Npad = 192 -> 64-channel tiles, three of them
     (64, 64, 64, 64, 128, 1, "stride2_scale"),     # 1x1 / stride 2 (the residual blocks' down-sampling convs), BatchNorm affine, no ReLU
     (37, 62, 62, 128, 256, 2, "stride2_scale"),    # the same: odd-sized output grid (31 x 31), grouped, ragged last tile
+    (457, 12, 12, 64, 64, 1, "up2"),               # up-sampled residual on an image that is no power of two (the decode divides), ragged last tile
+    (457, 12, 12, 64, 64, 1, "res_before"),        # the same image with a residual of the output's shape
 ]
 
 
