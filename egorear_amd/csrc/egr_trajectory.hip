@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "egr_common.h"
+#include "egr_trajectory_band.h"      // trj_band: row t of the penalty
 
 namespace {
 
@@ -66,15 +67,6 @@ __host__ __device__ inline void trj_decode(const trj_raw& r, trj_frame& o) {
     o.z[0] = on ? (double)r.x : 0.0;
     o.z[1] = on ? (double)r.y : 0.0;
     o.z[2] = on ? (double)r.z : 0.0;
-}
-
-// Row t of lv D1^T D1 + la D2^T D2: the diagonal a, A[t][t+1] = b and A[t][t+2] = c.  Row i of D2 (i = 1..T-2) holds (1, -2, 1) at
-// (i-1, i, i+1), so where T < 5 the band is narrower by itself.
-__host__ __device__ inline void trj_band(int t, int T, double lv, double la, double& a, double& b, double& c) {
-    const int mid = (t >= 1 && t <= T - 2) ? 1 : 0, up = (t + 1 <= T - 2) ? 1 : 0, dn = (t >= 2) ? 1 : 0;
-    a = lv * (double)((t > 0 ? 1 : 0) + (t < T - 1 ? 1 : 0)) + la * (double)(up + 4 * mid + dn);
-    b = t < T - 1 ? -lv - la * (double)(2 * (mid + up)) : 0.0;
-    c = up ? la : 0.0;
 }
 
 // The elimination's carried state for R right-hand sides.

@@ -43,6 +43,11 @@ weights.  `decode_clip_3d` chains heat maps of a clip -> Joints3D per frame -> T
 views' rays meet best, by Levenberg-Marquardt on `egr_rig_refine_f32` (DESIGN.md 5t), operator `egorear_amd::rig_refine`, not
 differentiable.  Its `coord_trans_mat` goes to every function above in place of the given one; `apply_rig_correction` composes a fitted
 correction with another clip's matrices, and `calibrate_rig` chains heat maps -> Joints2D -> RigFit.
+
+`fit_ray_tracks` is the triangulation and the smoother as one problem: per joint of a clip the track closest to the views' rays over
+the frames under the same penalties, on `egr_ray_track_f32` (DESIGN.md 5u), operator `egorear_amd::ray_track`, not differentiable - a
+frame one camera sees contributes its ray instead of being a gap, and the Huber form down-weights one bad view of a frame, not the
+frame.  `decode_clip_3d_rays` chains heat maps of a clip -> Joints2D -> RayTrack3D.
 """
 from __future__ import annotations
 
@@ -1015,3 +1020,106 @@ def calibrate_rig(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_t
     fit = refine_rig(joints2d.soft.detach(), joints2d.maxvals.detach(), cameras, coord_trans_mat, (H, W), threshold, min_det_ratio, fixed,
                      prior_weight, iterations, camera_calib_file_dir_path)
     return fit, joints2d
+
+
+# ---- ray-space clip smoothing --------------------------------------------------------------------------------------------------------
+
+@torch.library.custom_op("egorear_amd::ray_track", mutates_args=(), device_types="cuda")
+def ray_track_op(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
+                 threshold: float, vel_weight: float, accel_weight: float, huber: float, reweights: int, max_gap: int, min_pivot_ratio: float
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose (N, T, J, 3) cm, valid (N, T, J) uint8, residual (N, T, V, J) cm, weight (N, T, V, J), rays (N, T, J) uint8, energy (N, J)) of
+    coords (N, T, V, J, 2) * (sx, sy) = normalised image points, conf (N, T, V, J), cams (V, 30), ctm (N, T, V, 4, 4) or None:
+    egr_ray_track_f32.  No output is differentiable."""
+    hip._ray_track_operands(coords, conf, cams, ctm, sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio,
+                            "decode.ray_track", dense=False)
+    return hip.ray_track(_c(coords), _c(conf), _c(cams), _c(ctm), sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap,
+                         min_pivot_ratio)
+
+
+@ray_track_op.register_fake
+def _ray_track_fake(coords, conf, cams, ctm, sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio):
+    N, T, V, J = hip._ray_track_operands(coords, conf, cams, ctm, sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap,
+                                         min_pivot_ratio, "decode.ray_track", dense=False)
+    new = coords.new_empty
+    return (new((N, T, J, 3)), new((N, T, J), dtype=torch.uint8), new((N, T, V, J)), new((N, T, V, J)), new((N, T, J), dtype=torch.uint8),
+            new((N, J)))
+
+
+ray_track_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+
+
+class RayTrack3D(NamedTuple):
+    pose: torch.Tensor       # (N, T, J, 3) cm: the fitted track, written for every frame of a solvable track; 0 for the others
+    valid: torch.Tensor      # (N, T, J) bool: the track is solvable and a frame with a used ray is at most max_gap frames away
+    residual: torch.Tensor   # (N, T, V, J) cm: the distance of the pose from each used ray, 0 elsewhere
+    weight: torch.Tensor     # (N, T, V, J) the ray weights of the last solve: conf times the Huber factor, 0 for a ray that is not used
+    rays: torch.Tensor       # (N, T, J) uint8 the number of used rays of the frame
+    energy: torch.Tensor     # (N, J) the energy at the result
+
+
+def fit_ray_tracks(coords: torch.Tensor, conf: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                   heatmap_size: Tuple[float, float] = (64, 64), threshold: float = 0.5, accel_weight: float = 10.0, vel_weight: float = 0.0,
+                   huber_cm: float = 0.0, reweights: int = 0, max_gap: int = 8, min_pivot_ratio: float = 1e-10,
+                   camera_calib_file_dir_path: Optional[str] = None) -> RayTrack3D:
+    """coords (N, T, V, J, 2) - or (T, V, J, 2), one clip - and conf (N, T, V, J) of a clip, `cameras`, `heatmap_size`, `threshold` as for
+    `triangulate_joints`, `coord_trans_mat` (N, T, V, 4, 4) ((T, V, 4, 4) for one clip) or None -> RayTrack3D(pose, valid, residual,
+    weight, rays, energy): per joint of every clip the track that minimises
+      sum_t sum_v w_tv rho(dist(x_t, ray_tv)) + vel_weight sum |x_{t+1} - x_t|^2 + accel_weight sum |x_{t+1} - 2 x_t + x_{t-1}|^2,
+    w_tv = conf where the view is used, else 0 - the triangulation and the smoother in one problem, so that a frame one camera sees
+    contributes its ray (two of the point's three degrees of freedom) instead of being a gap, a near-parallel pair keeps what it
+    measures well while the penalty fixes the depth, and with huber_cm > 0 (`reweights` 1..16 rounds of IRLS after the plain solve) a
+    single bad view is down-weighted while the frame's other rays stay.  A frame without a used ray is filled from its neighbours.  A
+    track is solvable when it has enough rays for the penalty's null space (2 with vel_weight > 0; else 3 on 2 frames, or 2 in every
+    frame where T <= 2) and no pivot of its elimination falls to `min_pivot_ratio` of its largest diagonal entry; one that is not
+    gives zeros and valid False.  A frame is valid when a frame with a used ray is at most `max_gap` frames away.  Two launches;
+    nothing here is differentiable."""
+    what = "decode.fit_ray_tracks"
+    sx, sy = _scales(heatmap_size)
+    vel_weight, accel_weight, huber_cm, reweights, max_gap = _trj_parameters(accel_weight, vel_weight, huber_cm, reweights, max_gap)
+    one = coords.dim() == 4
+    if one:
+        coords, conf = coords.unsqueeze(0), conf.unsqueeze(0) if conf.dim() == 3 else conf
+        coord_trans_mat = None if coord_trans_mat is None else coord_trans_mat.unsqueeze(0)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, coords.device)
+    hip._ray_track_operands(coords, conf, cams, coord_trans_mat, sx, sy, threshold, vel_weight, accel_weight, huber_cm, reweights, max_gap,
+                            min_pivot_ratio, what, dense=False)
+    hip._on_device(what, coords, conf, coord_trans_mat, exc=ValueError)
+    pose, valid, residual, weight, rays, energy = ray_track_op(coords, conf, cams, coord_trans_mat, sx, sy, float(threshold), vel_weight,
+                                                               accel_weight, huber_cm, reweights, max_gap, float(min_pivot_ratio))
+    track = RayTrack3D(pose, valid.view(torch.bool), residual, weight, rays, energy)
+    return RayTrack3D(*(t.squeeze(0) for t in track)) if one else track
+
+
+def decode_clip_3d_rays(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                        beta: float = 100.0, threshold: float = 0.5, accel_weight: float = 10.0, vel_weight: float = 0.0, huber_cm: float = 0.0,
+                        reweights: int = 0, max_gap: int = 8, min_pivot_ratio: float = 1e-10,
+                        camera_calib_file_dir_path: Optional[str] = None) -> Tuple[Joints2D, RayTrack3D]:
+    """heatmaps (N, T, V, J, H, W) - or (T, V, J, H, W), one clip - -> (Joints2D, RayTrack3D): `decode_joints_2d` on the N * T frames
+    (soft-argmax), then `fit_ray_tracks` of its sub-pixel joints weighted by the maps' maxima - the soft-argmax launch and the two of
+    the fit with nothing between them, bit-identical to calling the pieces.  No per-frame triangulation happens: a joint one camera
+    sees is a ray, not a gap.  Both results come in the clip's shape: Joints2D fields (N, T, V, J, ...).  Not differentiable."""
+    what = "decode.decode_clip_3d_rays"
+    one = heatmaps.dim() == 5
+    if one:
+        heatmaps = heatmaps.unsqueeze(0)
+        coord_trans_mat = None if coord_trans_mat is None else coord_trans_mat.unsqueeze(0)
+    if heatmaps.dim() != 6 or not 2 <= heatmaps.shape[2] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (N, T, V, J, H, W) or (T, V, J, H, W) with 2 to 4 views, got "
+                         f"{tuple(heatmaps.shape)}")
+    _check(heatmaps, float(beta), MODE_SOFTMAX, dims=6, what="decode_clip_3d_rays")
+    N, T, V, J, H, W = (int(v) for v in heatmaps.shape)
+    # (what the fit would refuse is refused before the soft-argmax runs)
+    vel_weight, accel_weight, huber_cm, reweights, max_gap = _trj_parameters(accel_weight, vel_weight, huber_cm, reweights, max_gap)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, heatmaps.device)
+    hip._ray_track_operands(heatmaps.new_empty((N, T, V, J, 2), device="meta"), heatmaps.new_empty((N, T, V, J), device="meta"), cams,
+                            coord_trans_mat, 1.0 / W, 1.0 / H, threshold, vel_weight, accel_weight, huber_cm, reweights, max_gap, min_pivot_ratio,
+                            what, dense=False)
+    hip._on_device(what, heatmaps, coord_trans_mat, exc=ValueError)
+    flat = decode_joints_2d(heatmaps.reshape((N * T, V, J, H, W)), beta=beta, threshold=threshold)
+    joints2d = Joints2D(flat.soft.view(N, T, V, J, 2), flat.hard.view(N, T, V, J, 2), flat.maxvals.view(N, T, V, J), flat.valid.view(N, T, V, J))
+    track = fit_ray_tracks(joints2d.soft.detach(), joints2d.maxvals.detach(), cameras, coord_trans_mat, (H, W), threshold, accel_weight,
+                           vel_weight, huber_cm, reweights, max_gap, min_pivot_ratio, camera_calib_file_dir_path)
+    if one:
+        joints2d, track = Joints2D(*(t.squeeze(0) for t in joints2d)), RayTrack3D(*(t.squeeze(0) for t in track))
+    return joints2d, track

@@ -192,6 +192,7 @@ EXPORTS = [
     "egr_triangulate_f32", "egr_triangulate_bwd_f32", "egr_volume_fuse_f32", "egr_volume_fuse_bwd_f32",
     "egr_peaks_f32", "egr_consensus_f32", "egr_skeleton_fit_f32", "egr_bone_lengths_f32", "egr_skeleton_resize_f32",
     "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32", "egr_rig_refine_f32", "egr_rig_refine_workspace_bytes",
+    "egr_ray_track_f32", "egr_ray_track_workspace_bytes",
 ]
 
 
@@ -334,6 +335,10 @@ def _load() -> C.CDLL:
     lib.egr_rig_refine_workspace_bytes.argtypes = [i32, i32, i32]
     lib.egr_rig_refine_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, i32, f32, i32, vp, i64, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp]
+    lib.egr_ray_track_workspace_bytes.restype = C.c_int64
+    lib.egr_ray_track_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.egr_ray_track_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, i32, i32, C.c_double, vp, i64, vp, vp, vp,
+                                      vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -375,7 +380,8 @@ def _load() -> C.CDLL:
     for name in EXPORTS:
         getattr(lib, name)  # fail at import if a symbol is missing
         if name not in ("egr_version", "egr_w6_elems", "egr_stem_w6_bytes", "egr_wh2_elems", "egr_stem_wh2_bytes", "egr_wstream_image_bytes",
-                        "egr_linear_wstream_workspace_bytes", "egr_rig_refine_workspace_bytes"):
+                        "egr_linear_wstream_workspace_bytes", "egr_rig_refine_workspace_bytes",
+                        "egr_ray_track_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     return lib
 
@@ -1805,6 +1811,22 @@ TRAJECTORY_MAX_REWEIGHTS = 16
 TRAJECTORY_FWD_SLOTS, TRAJECTORY_BWD_SLOTS = 5, 8      # fp64 workspace planes of T * N * J: the two sub-diagonals and 3 / 6 right-hand sides
 
 
+def _trajectory_parameters(what: str, vel_weight, accel_weight, huber, reweights, max_gap):
+    """The penalty, Huber and gap conventions of the clip decoders (egr_trajectory.hip, egr_raytrack.hip)."""
+    _non_negative(what, "vel_weight", vel_weight)
+    _non_negative(what, "accel_weight", accel_weight)
+    if not (vel_weight > 0.0 or accel_weight > 0.0):
+        raise ValueError(f"egorear_amd.{what}: vel_weight and accel_weight must not both be zero")
+    _non_negative(what, "huber", huber)
+    if not _int_in(reweights, 0, TRAJECTORY_MAX_REWEIGHTS):
+        raise ValueError(f"egorear_amd.{what}: reweights must be an integer in 0..{TRAJECTORY_MAX_REWEIGHTS}, got {reweights!r}")
+    if (reweights > 0) != (huber > 0.0):
+        raise ValueError(f"egorear_amd.{what}: huber > 0 and reweights > 0 go together (the plain form has both 0), got huber {huber!r}, "
+                         f"reweights {reweights!r}")
+    if not _int_in(max_gap, 0, (1 << 31) - 1):
+        raise ValueError(f"egorear_amd.{what}: max_gap must be a non-negative integer, got {max_gap!r}")
+
+
 def _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, reweights, max_gap, what: str, g_pose=None, dense: bool = True):
     """(N, T, J) of a trajectory launch; every shape / dtype / parameter error as ValueError."""
     if pose.dim() != 4 or pose.shape[-1] != 3:
@@ -1821,18 +1843,7 @@ def _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, huber, rew
     if obs is not None:
         _flags(what, obs, (N, T, J), "observed")
     _float32(what, (pose, "pose"), (weight, "weight"))
-    _non_negative(what, "vel_weight", vel_weight)
-    _non_negative(what, "accel_weight", accel_weight)
-    if not (vel_weight > 0.0 or accel_weight > 0.0):
-        raise ValueError(f"egorear_amd.{what}: vel_weight and accel_weight must not both be zero")
-    _non_negative(what, "huber", huber)
-    if not _int_in(reweights, 0, TRAJECTORY_MAX_REWEIGHTS):
-        raise ValueError(f"egorear_amd.{what}: reweights must be an integer in 0..{TRAJECTORY_MAX_REWEIGHTS}, got {reweights!r}")
-    if (reweights > 0) != (huber > 0.0):
-        raise ValueError(f"egorear_amd.{what}: huber > 0 and reweights > 0 go together (the plain form has both 0), got huber {huber!r}, "
-                         f"reweights {reweights!r}")
-    if not _int_in(max_gap, 0, (1 << 31) - 1):
-        raise ValueError(f"egorear_amd.{what}: max_gap must be a non-negative integer, got {max_gap!r}")
+    _trajectory_parameters(what, vel_weight, accel_weight, huber, reweights, max_gap)
     _cotangents(what, (g_pose, (N, T, J, 3), "g_pose"))
     _contiguous(what, dense, (pose, "pose"), (weight, "weight"), (obs, "observed"), (g_pose, "g_pose"))
     return N, T, J
@@ -1878,6 +1889,67 @@ def trajectory_smooth_bwd(pose: torch.Tensor, weight: Optional[torch.Tensor], ob
             float(vel_weight), float(accel_weight), _p(ws, torch.float64), _p(g_in), _p(g_weight), _stream(), flops=N * T * J * 2.0 * 70.0,
             nbytes=N * T * J * (2.0 * 64.0 + 2.0 * 17.0 + 12.0 + 16.0))
     return g_in, g_weight
+
+
+RAY_TRACK_RAY_SLOTS, RAY_TRACK_SOLVE_SLOTS = 4, 18    # fp64 workspace planes of T * N * J: d[3], w a view; E (9), D^-1 (6), q (3)
+
+
+def _ray_track_operands(coords, conf, cams, ctm, sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio,
+                        what: str, dense: bool = True):
+    """(N, T, V, J) of a ray-track launch; every shape / dtype / parameter error as ValueError."""
+    if coords.dim() != 5 or coords.shape[-1] != 2:
+        raise ValueError(f"egorear_amd.{what}: coords must be (N, T, V, J, 2), got {tuple(coords.shape)}")
+    N, T, V, J = (int(v) for v in coords.shape[:4])
+    if N < 1 or T < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty coords {tuple(coords.shape)}")
+    if T > TRAJECTORY_MAX_T:
+        raise ValueError(f"egorear_amd.{what}: at most {TRAJECTORY_MAX_T} frames a clip are supported, got {T}")
+    if tuple(conf.shape) != (N, T, V, J):
+        raise ValueError(f"egorear_amd.{what}: conf must be {(N, T, V, J)}, got {tuple(conf.shape)}")
+    if not 2 <= V <= 4:
+        raise ValueError(f"egorear_amd.{what}: 2 to 4 views are supported, got {V}")
+    if tuple(cams.shape) != (V, RAY_REC):
+        raise ValueError(f"egorear_amd.{what}: cams must be {(V, RAY_REC)} (camera.packed_rays()), got {tuple(cams.shape)}")
+    if ctm is not None and tuple(ctm.shape) != (N, T, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(N, T, V, 4, 4)}, got {tuple(ctm.shape)}")
+    if N * T * V * J * 2 >= 1 << 31:
+        raise ValueError(f"egorear_amd.{what}: N * T * V * J * 2 must stay below 2^31, got {tuple(coords.shape)}")
+    _float32(what, (coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    _positive(what, "the coordinate scales", sx, sy)
+    if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == threshold):
+        raise ValueError(f"egorear_amd.{what}: threshold must be a number, got {threshold!r}")
+    _trajectory_parameters(what, vel_weight, accel_weight, huber, reweights, max_gap)
+    if not (isinstance(min_pivot_ratio, (int, float)) and not isinstance(min_pivot_ratio, bool) and 0.0 <= min_pivot_ratio < 1.0):
+        raise ValueError(f"egorear_amd.{what}: min_pivot_ratio must be a number in [0, 1), got {min_pivot_ratio!r}")
+    _contiguous(what, dense, (coords, "coords"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    return N, T, V, J
+
+
+def ray_track(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None, sx: float = 1.0,
+              sy: float = 1.0, threshold: float = 0.5, vel_weight: float = 0.0, accel_weight: float = 10.0, huber: float = 0.0,
+              reweights: int = 0, max_gap: int = 8, min_pivot_ratio: float = 1e-10):
+    """coords (N,T,V,J,2), conf (N,T,V,J), cams (V,30) = camera.packed_rays(), ctm (N,T,V,4,4) | None (the syn rig) -> pose (N,T,J,3) cm,
+    valid (N,T,J) u8, residual (N,T,V,J) cm, weight (N,T,V,J), rays (N,T,J) u8, energy (N,J): egr_ray_track_f32, per joint of every clip
+    the track that is closest to the views' rays over the frames under a velocity and an acceleration penalty (include/egorear_hip.h
+    states the energy, the Huber reweighting, the solvability and the validity rule).  The fp64 workspace is allocated here, like the
+    outputs.  Two launches behind the one entry."""
+    N, T, V, J = _ray_track_operands(coords, conf, cams, ctm, sx, sy, threshold, vel_weight, accel_weight, huber, reweights, max_gap,
+                                     min_pivot_ratio, "ray_track")
+    _on_device("ray_track", coords, conf, cams, ctm)
+    dev = coords.device
+    nbytes_ws = int(lib.egr_ray_track_workspace_bytes(N, T, V, J))
+    ws = torch.empty((nbytes_ws // 8,), device=dev, dtype=torch.float64)
+    pose = torch.empty((N, T, J, 3), device=dev, dtype=torch.float32)
+    valid, rays = (torch.empty((N, T, J), device=dev, dtype=torch.uint8) for _ in range(2))
+    residual, weight = (torch.empty((N, T, V, J), device=dev, dtype=torch.float32) for _ in range(2))
+    energy = torch.empty((N, J), device=dev, dtype=torch.float32)
+    solves = reweights + 1.0
+    _launch("egr_ray_track_f32", lib.egr_ray_track_f32, _p(coords), _p(conf), _p(cams), _p(ctm), N, T, V, J, float(sx), float(sy),
+            float(threshold), float(vel_weight), float(accel_weight), float(huber), int(reweights), int(max_gap), float(min_pivot_ratio),
+            _p(ws, torch.float64), nbytes_ws, _p(pose), _p(valid, torch.uint8), _p(residual), _p(weight), _p(rays, torch.uint8), _p(energy),
+            _stream(), flops=N * T * J * (solves * (V * 90.0 + 330.0) + V * 60.0),
+            nbytes=N * T * J * (V * (12.0 + 32.0) + solves * (V * 32.0 + 3.0 * 144.0 + 24.0) + V * 40.0 + 38.0))
+    return pose, valid, residual, weight, rays, energy
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -689,6 +689,43 @@ int egr_rig_refine_f32(const float* coords, const float* conf, const float* cams
                        float* matrix /* V x 3 x 3 */, float* ctm_out /* B x V x 4 x 4 */, float* cost0, float* cost, int32_t* pairs,
                        int32_t* steps, float* grad, uint8_t* valid, void* stream);
 
+/* Ray-space clip smoothing: the 3-D tracks of a clip fitted to the views' rays directly.  A track is one joint j of one
+ * clip n, T frames; with the rays, weights and extrinsics of egr_triangulate_f32 at frame b = n T + t (w_tv = conf where the view is
+ * used - conf >= threshold, conf > 0, conf and coords finite - else 0, and what stands there is never read) it minimises over x_0..x_{T-1} (cm)
+ *   E(x) = sum_t sum_v w_tv rho(|P_tv (R_tv x_t + t_tv)|) + vel_weight sum_{t=0}^{T-2} |x_{t+1} - x_t|^2
+ *                                                         + accel_weight sum_{t=1}^{T-2} |x_{t+1} - 2 x_t + x_{t-1}|^2,   P = I - d d^T,
+ * rho as in egr_trajectory_smooth_f32 (the square, or Huber's function of the ray distance at huber > 0).  coords (N, T, V, J, 2),
+ * conf (N, T, V, J), cams (V, 30) ray records, ctm NULL (the syn rig) or (N, T, V, 4, 4).  A frame without a used ray is a gap that
+ * its neighbours fill; a frame with one used ray contributes that ray: two of the point's three degrees of freedom.
+ *   Plain form: x solves the 3T x 3T system  (blockdiag(G_t) + (vel_weight D1^T D1 + accel_weight D2^T D2) (x) I_3) x = (g_t),
+ *   G_t = sum_v w_tv R^T P R and g_t = -sum_v w_tv R^T P t the normal equations of frame t's rays - block pentadiagonal.
+ *   Robust form (huber > 0, reweights = K in 1..16): x(0) the plain solve; x(k+1) solves the plain problem with the ray weights
+ *   w_tv min(1, huber / dist_tv(x(k))); K + 1 solves, always.  E does not increase from one k to the next.
+ *   A track is solvable when (a) with vel_weight > 0 it has 2 used rays or more; with vel_weight == 0 and T >= 3, 3 used rays or more
+ *   on 2 frames or more; with vel_weight == 0 and T <= 2, 2 used rays or more in every frame; and (b) every scalar pivot of the
+ *   elimination below, in the plain solve, exceeds min_pivot_ratio x the largest diagonal entry of the track's matrix (a NaN fails).
+ *   A track that is not solvable gives 0 in every output.
+ *   Elimination: block LDL^T along t without pivoting, D_t = G_t + a_t I - E_{t-1} D_{t-1} E_{t-1}^T - F_{t-2} D_{t-2} F_{t-2}^T with
+ *   (a_t, b_t, c_t) row t of the penalty, E_t = (b_t I - c_{t-1} E_{t-1}^T) D_t^-1, F_t = c_t D_t^-1; every D_t by the 3 x 3 LDL^T of
+ *   the triangulation (no pivoting, coordinate order x, y, z): its three d are the scalar pivots of rule (b), 3T a track.
+ * pose (N, T, J, 3): written for every frame of a solvable track; valid (N, T, J): 1 iff the track is solvable and a frame with a used
+ * ray is at most max_gap frames away; residual (N, T, V, J): the ray distance at the result for used rays, 0 elsewhere; weight
+ * (N, T, V, J): the ray weights of the last solve; rays (N, T, J): the number of used rays; energy (N, J): E at the result with the
+ * base weights.  workspace: egr_ray_track_workspace_bytes(N, T, V, J) bytes = (4 V + 18) T N J doubles (0 for shapes the entry
+ * refuses), contents unspecified before and after.  The parameters are taken as fp32 except min_pivot_ratio.
+ * Two launches on `stream`, no host synchronisation: the ray pass (a thread per (frame, joint): the views' unit rays and weights in
+ * fp64, planes of T x N J), then the solve - one lane per track, the tracks of a clip in adjacent lanes, every sweep of the K + 1
+ * solves and the energy pass inside it.  No atomics, a fixed order: the same bits every run, alone or in a batch.  Latency-bound.
+ * EGR_EINVAL: N or J < 1, V outside 2..4, T outside 1..4096, N*T*V*J*2 >= 2^31, sx or sy not positive and finite, threshold NaN, the
+ * penalties, huber, reweights and max_gap as egr_trajectory_smooth_f32 refuses them, min_pivot_ratio negative, NaN or >= 1;
+ * EGR_EWORKSPACE: workspace_bytes too small. */
+int64_t egr_ray_track_workspace_bytes(int32_t N, int32_t T, int32_t V, int32_t J);
+int egr_ray_track_f32(const float* coords, const float* conf, const float* cams, const float* ctm /* nullable */, int32_t N, int32_t T,
+                      int32_t V, int32_t J, float sx, float sy, float threshold, float vel_weight, float accel_weight, float huber,
+                      int32_t reweights, int32_t max_gap, double min_pivot_ratio, double* workspace, int64_t workspace_bytes,
+                      float* pose /* N x T x J x 3 */, uint8_t* valid /* N x T x J */, float* residual /* N x T x V x J */,
+                      float* weight /* N x T x V x J */, uint8_t* rays /* N x T x J */, float* energy /* N x J */, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,

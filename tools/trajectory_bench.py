@@ -67,6 +67,33 @@ def moving_skeleton(T, parents, gen, torch):
     return root + turned + swing
 
 
+def rendered_clip(T, parents, rec, gen, torch, FS):
+    """The accuracy clip (tools/ray_track_bench.py renders the same one): truth (T, J, 3) float64, maps (T, 4, J, HM, HM) fp32 on the
+    host, glitch and dropped (T, J) bool - sigma-1 bumps at the syn rig's projections with PIXEL_NOISE on every centre, GLITCHES pairs
+    rendered GLITCH_CM off in every view, DROPPED of the other pairs keeping one view."""
+    truth = moving_skeleton(T, parents, gen, torch)
+    shown = truth.clone()
+    glitch = torch.zeros(T, J, dtype=torch.bool)
+    while int(glitch.sum()) < GLITCHES:
+        t, j = int(torch.randint(2, T - 2, (1,), generator=gen)), int(torch.randint(0, J, (1,), generator=gen))
+        if not bool(glitch[max(t - 2, 0):t + 3, j].any()):
+            glitch[t, j] = True
+            u = torch.randn(3, generator=gen, dtype=torch.float64)
+            u[2] = 0.0                                                                 # (sideways: it stays in front of the cameras)
+            shown[t, j] += GLITCH_CM * u / u.norm()
+    x, y, _ = FS.heatmap_coords(shown.unsqueeze(1).unsqueeze(3), rec, None, FS.HM, FS.HM)
+    x = x.squeeze(-1) + PIXEL_NOISE * torch.randn(T, 4, J, generator=gen, dtype=torch.float64)
+    y = y.squeeze(-1) + PIXEL_NOISE * torch.randn(T, 4, J, generator=gen, dtype=torch.float64)
+    maps = FS.render(x, y, FS.HM, FS.HM).float()
+    dropped = (torch.rand(T, J, generator=gen) < DROPPED) & ~glitch
+    for t, j in dropped.nonzero().tolist():
+        keep = int(torch.randint(0, 4, (1,), generator=gen))
+        for v in range(4):
+            if v != keep:
+                maps[t, v, j] = 0.0
+    return truth, maps, glitch, dropped
+
+
 def graph_times(launches, inputs, rounds, torch):
     graphs, keep = {}, []
     for name, fn in launches.items():
@@ -112,26 +139,7 @@ def main():
 
     # ---- the rendered clip (also the chain's maps)
     T = 64
-    truth = moving_skeleton(T, parents, gen, torch)
-    shown = truth.clone()
-    glitch = torch.zeros(T, J, dtype=torch.bool)
-    while int(glitch.sum()) < GLITCHES:
-        t, j = int(torch.randint(2, T - 2, (1,), generator=gen)), int(torch.randint(0, J, (1,), generator=gen))
-        if not bool(glitch[max(t - 2, 0):t + 3, j].any()):
-            glitch[t, j] = True
-            u = torch.randn(3, generator=gen, dtype=torch.float64)
-            u[2] = 0.0                                                                 # (sideways: it stays in front of the cameras)
-            shown[t, j] += GLITCH_CM * u / u.norm()
-    x, y, _ = FS.heatmap_coords(shown.unsqueeze(1).unsqueeze(3), rec, None, FS.HM, FS.HM)
-    x = x.squeeze(-1) + PIXEL_NOISE * torch.randn(T, 4, J, generator=gen, dtype=torch.float64)
-    y = y.squeeze(-1) + PIXEL_NOISE * torch.randn(T, 4, J, generator=gen, dtype=torch.float64)
-    maps = FS.render(x, y, FS.HM, FS.HM).float()
-    dropped = (torch.rand(T, J, generator=gen) < DROPPED) & ~glitch
-    for t, j in dropped.nonzero().tolist():
-        keep = int(torch.randint(0, 4, (1,), generator=gen))
-        for v in range(4):
-            if v != keep:
-                maps[t, v, j] = 0.0
+    truth, maps, glitch, dropped = rendered_clip(T, parents, rec, gen, torch, FS)
     maps = maps.contiguous().to(dev)
     chain_maps = [maps] + [(maps + 0.01 * torch.randn(maps.shape, generator=gen).to(dev)).contiguous() for _ in range(a.inputs - 1)]
 
