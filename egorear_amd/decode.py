@@ -48,6 +48,12 @@ correction with another clip's matrices, and `calibrate_rig` chains heat maps ->
 the frames under the same penalties, on `egr_ray_track_f32` (DESIGN.md 5u), operator `egorear_amd::ray_track`, not differentiable - a
 frame one camera sees contributes its ray instead of being a gap, and the Huber form down-weights one bad view of a frame, not the
 frame.  `decode_clip_3d_rays` chains heat maps of a clip -> Joints2D -> RayTrack3D.
+
+`joint_information` is how well the views fix a point: the 3 x 3 information matrix of the pixel reprojection at a 3-D point, on
+`egr_joint_info_f32`, operator `egorear_amd::joint_info`; `smooth_trajectory_info` is `smooth_trajectory` with that matrix in place of
+the scalar weight, on `egr_info_track_f32`, operator `egorear_amd::info_track` (DESIGN.md 5v) - the range, which a near-parallel pair
+measures badly, is smoothed hard and the directions across it barely.  Neither is differentiable.  `decode_clip_3d_info` chains heat
+maps of a clip -> Joints3D -> Track3D (the linearisation track) -> Information3D at that track -> InfoTrack3D, five launches.
 """
 from __future__ import annotations
 
@@ -1123,3 +1129,169 @@ def decode_clip_3d_rays(heatmaps: torch.Tensor, cameras: Union[str, Sequence], c
     if one:
         joints2d, track = Joints2D(*(t.squeeze(0) for t in joints2d)), RayTrack3D(*(t.squeeze(0) for t in track))
     return joints2d, track
+
+
+# ---- information-weighted clip smoothing ---------------------------------------------------------------------------------------------
+
+@torch.library.custom_op("egorear_amd::joint_info", mutates_args=(), device_types="cuda")
+def joint_info_op(points: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor], sx: float, sy: float,
+                  threshold: float, min_det_ratio: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(info (B, J, 6), views (B, J) uint8, sigma (B, J), valid (B, J) uint8) of points (B, J, 3) cm, conf (B, V, J), cams (V, 30), ctm
+    (B, V, 4, 4) or None: egr_joint_info_f32.  No output is differentiable."""
+    hip._joint_info_operands(points, conf, cams, ctm, sx, sy, threshold, min_det_ratio, "decode.joint_info", dense=False)
+    return hip.joint_info(_c(points), _c(conf), _c(cams), _c(ctm), sx, sy, threshold, min_det_ratio)
+
+
+@joint_info_op.register_fake
+def _joint_info_fake(points, conf, cams, ctm, sx, sy, threshold, min_det_ratio):
+    B, _, J = hip._joint_info_operands(points, conf, cams, ctm, sx, sy, threshold, min_det_ratio, "decode.joint_info", dense=False)
+    new = points.new_empty
+    return new((B, J, 6)), new((B, J), dtype=torch.uint8), new((B, J)), new((B, J), dtype=torch.uint8)
+
+
+@torch.library.custom_op("egorear_amd::info_track", mutates_args=(), device_types="cuda")
+def info_track_op(pose: torch.Tensor, info: torch.Tensor, obs: Optional[torch.Tensor], vel_weight: float, accel_weight: float, huber: float,
+                  reweights: int, max_gap: int, min_pivot_ratio: float
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose_out (N, T, J, 3) cm, valid (N, T, J) uint8, residual (N, T, J) in coordinate units, weight (N, T, J), energy (N, J)) of pose
+    (N, T, J, 3), info (N, T, J, 6), obs (N, T, J) uint8 or None: egr_info_track_f32.  No output is differentiable."""
+    hip._info_track_operands(pose, info, obs, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio, "decode.info_track",
+                             dense=False)
+    return hip.info_track(_c(pose), _c(info), _c(obs), vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio)
+
+
+@info_track_op.register_fake
+def _info_track_fake(pose, info, obs, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio):
+    N, T, J = hip._info_track_operands(pose, info, obs, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio,
+                                       "decode.info_track", dense=False)
+    new = pose.new_empty
+    return new((N, T, J, 3)), new((N, T, J), dtype=torch.uint8), new((N, T, J)), new((N, T, J)), new((N, J))
+
+
+joint_info_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+info_track_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+
+
+class Information3D(NamedTuple):
+    info: torch.Tensor       # (B, J, 6) the information matrix sum_v conf_v J_v^T J_v in the order (00, 01, 02, 11, 12, 22), coordinate units^2 / cm^2
+    views: torch.Tensor      # (B, J) uint8 the views that entered
+    sigma: torch.Tensor      # (B, J) sqrt(trace(info^-1)): cm of positional standard deviation per unit of coordinate noise; 0 where not valid
+    valid: torch.Tensor      # (B, J) bool: the matrix is positive definite and not too flat for its size (min_det_ratio)
+
+
+class InfoTrack3D(NamedTuple):
+    pose: torch.Tensor       # (N, T, J, 3) cm: the smoothed track, written for every frame of a solvable track; 0 for the others
+    valid: torch.Tensor      # (N, T, J) bool: the track is solvable and a used frame is at most max_gap frames away
+    residual: torch.Tensor   # (N, T, J) sqrt((pose - z)^T W (pose - z)) at used frames, in coordinate units (pixels); 0 elsewhere
+    weight: torch.Tensor     # (N, T, J) the Huber factors of the last solve (1 in the plain form), 0 for a gap
+    energy: torch.Tensor     # (N, J) the energy at the result
+
+
+INFO_ACCEL_WEIGHT = 1.0      # the default accel_weight of the matrix-weighted smoother: the rendered clip's sweep set it (DESIGN.md 5v)
+
+
+def joint_information(points: torch.Tensor, conf: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                      heatmap_size: Tuple[float, float] = (64, 64), threshold: float = 0.5, min_det_ratio: float = 1e-6,
+                      camera_calib_file_dir_path: Optional[str] = None) -> Information3D:
+    """points (B, J, 3) cm in the device frame, conf (B, V, J), `cameras`, `coord_trans_mat`, `heatmap_size`, `threshold` as for
+    `triangulate_joints` -> Information3D(info, views, sigma, valid): per point W = sum_v conf_v J_v^T J_v, J_v the 2 x 3 Jacobian of
+    view v's fisheye projection in pixels of a `heatmap_size` map - how well the views that see the point (conf >= threshold, and the
+    point projects off the optical axis) fix it in each direction.  With unit pixel noise W^-1 is the covariance of the triangulated
+    point: `sigma` = sqrt(trace(W^-1)) cm per pixel, several times larger along the range than across for the front pair.  It takes no
+    coordinates: the matrix depends on where the point is, not on where it was observed.  One launch; not differentiable."""
+    what = "decode.joint_information"
+    sx, sy = _scales(heatmap_size)
+    cams = _ray_records(cameras, camera_calib_file_dir_path, points.device)
+    hip._joint_info_operands(points, conf, cams, coord_trans_mat, sx, sy, threshold, float(min_det_ratio), what, dense=False)
+    hip._on_device(what, points, conf, coord_trans_mat, exc=ValueError)
+    info, views, sigma, valid = joint_info_op(points, conf, cams, coord_trans_mat, sx, sy, float(threshold), float(min_det_ratio))
+    return Information3D(info, views, sigma, valid.view(torch.bool))
+
+
+def _info_parameters(accel_weight, vel_weight, huber_px, reweights, max_gap):
+    try:
+        return float(vel_weight), float(accel_weight), float(huber_px), reweights, max_gap
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.decode.smooth_trajectory_info: accel_weight, vel_weight and huber_px must be numbers, got "
+                         f"{accel_weight!r}, {vel_weight!r}, {huber_px!r}") from None
+
+
+def smooth_trajectory_info(pose: torch.Tensor, info: torch.Tensor, observed: Optional[torch.Tensor] = None,
+                           accel_weight: float = INFO_ACCEL_WEIGHT, vel_weight: float = 0.0, huber_px: float = 0.0, reweights: int = 0,
+                           max_gap: int = 8, min_pivot_ratio: float = 1e-10) -> InfoTrack3D:
+    """pose (N, T, J, 3) cm - or (T, J, 3), one clip - with info (N, T, J, 6) (`Information3D.info`) and observed (N, T, J) bool / uint8
+    (None: every frame; `Joints3D.valid` plugs in) -> InfoTrack3D(pose, valid, residual, weight, energy): per joint of every clip the
+    track that minimises
+      sum_t rho(r_t) + vel_weight sum |x_{t+1} - x_t|^2 + accel_weight sum |x_{t+1} - 2 x_t + x_{t-1}|^2,   r_t^2 = (x_t - z_t)^T W_t (x_t - z_t)
+    - `smooth_trajectory` with a 3 x 3 matrix in place of the scalar weight, so that a direction the cameras measure badly (the range,
+    for the front pair) is smoothed hard and a direction they measure well barely.  A frame is used when it is observed, its pose and
+    matrix are finite, the matrix's diagonal is >= 0 and its trace > 0; any other frame is a gap, filled from its neighbours, and what
+    stands in it is never read.  A rank-2 matrix (one view) is a legitimate frame.  r_t is the displacement in pixels, so `huber_px` is
+    a radius in pixels: with huber_px > 0, `reweights` (1..16) rounds of iteratively reweighted least squares follow the plain solve.
+    A track without enough used frames (one with vel_weight > 0, else two, every frame where T <= 2), or whose elimination meets a
+    pivot at or below `min_pivot_ratio` of its largest diagonal entry, gives zeros and valid False.  A frame is valid when a used
+    frame is at most `max_gap` frames away.  The penalties are in pixel^2 / cm^2: accel_weight here is not `smooth_trajectory`'s.  One
+    launch; nothing here is differentiable."""
+    what = "decode.smooth_trajectory_info"
+    vel_weight, accel_weight, huber_px, reweights, max_gap = _info_parameters(accel_weight, vel_weight, huber_px, reweights, max_gap)
+    one = pose.dim() == 3
+    if one:
+        pose, info = pose.unsqueeze(0), info.unsqueeze(0) if info.dim() == 3 else info
+        observed = None if observed is None else observed.unsqueeze(0)
+    if observed is not None:
+        observed = _as_flags(observed)
+    hip._info_track_operands(pose, info, observed, vel_weight, accel_weight, huber_px, reweights, max_gap, min_pivot_ratio, what, dense=False)
+    hip._on_device(what, pose, info, observed, exc=ValueError)
+    out, valid, residual, weight, energy = info_track_op(pose, info, observed, vel_weight, accel_weight, huber_px, reweights, max_gap,
+                                                         float(min_pivot_ratio))
+    track = InfoTrack3D(out, valid.view(torch.bool), residual, weight, energy)
+    return InfoTrack3D(*(t.squeeze(0) for t in track)) if one else track
+
+
+def decode_clip_3d_info(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_trans_mat: Optional[torch.Tensor] = None,
+                        beta: float = 100.0, threshold: float = 0.5, min_det_ratio: float = 1e-6, linearise_accel_weight: float = 10.0,
+                        accel_weight: float = INFO_ACCEL_WEIGHT, vel_weight: float = 0.0, huber_px: float = 0.0, reweights: int = 0,
+                        max_gap: int = 8, min_pivot_ratio: float = 1e-10, camera_calib_file_dir_path: Optional[str] = None
+                        ) -> Tuple[Joints3D, Track3D, InfoTrack3D]:
+    """heatmaps (N, T, V, J, H, W) - or (T, V, J, H, W), one clip - -> (Joints3D, Track3D, InfoTrack3D): soft-argmax, triangulation,
+    `smooth_trajectory` in its plain form at `linearise_accel_weight` (the first two results are `decode_clip_3d`'s, bit for bit), then
+    `joint_information` AT THAT SMOOTHED TRACK with the soft-argmax confidences, then `smooth_trajectory_info` of the TRIANGULATED poses
+    with observed = Joints3D.valid - five launches with nothing between them, bit-identical to calling the pieces.
+    Why the matrices are taken at the smoothed track and not at the triangulated points: a matrix evaluated at a frame's own noisy
+    point correlates with that frame's error - a point triangulated too near the rig projects with larger Jacobians and so gets more
+    weight, and the weighted track is pulled towards the rig (`fit_ray_tracks` fails the same way: a ray distance in cm favours nearer
+    points).  The scalar-smoothed track averages the noise of many frames, so matrices taken there are nearly independent of the
+    frame's own error and the weighting is unbiased (DESIGN.md 5v has the argument and the measurements).  Not differentiable past the
+    first two results."""
+    what = "decode.decode_clip_3d_info"
+    one = heatmaps.dim() == 5
+    if one:
+        heatmaps = heatmaps.unsqueeze(0)
+        coord_trans_mat = None if coord_trans_mat is None else coord_trans_mat.unsqueeze(0)
+    if heatmaps.dim() != 6 or not 2 <= heatmaps.shape[2] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (N, T, V, J, H, W) or (T, V, J, H, W) with 2 to 4 views, got "
+                         f"{tuple(heatmaps.shape)}")
+    N, T, V, J, H, W = (int(v) for v in heatmaps.shape)
+    if coord_trans_mat is not None and tuple(coord_trans_mat.shape) != (N, T, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(N, T, V, 4, 4)}, got {tuple(coord_trans_mat.shape)}")
+    # (what the two smoothers would refuse is refused before the soft-argmax runs)
+    vel_weight, accel_weight, huber_px, reweights, max_gap = _info_parameters(accel_weight, vel_weight, huber_px, reweights, max_gap)
+    _, lin_weight, _, _, _ = _trj_parameters(linearise_accel_weight, 0.0, 0.0, 0, max_gap)
+    meta = lambda *shape: heatmaps.new_empty(shape, device="meta")
+    hip._trajectory_operands(meta(N, T, J, 3), None, None, 0.0, lin_weight, 0.0, 0, max_gap, what, dense=False)
+    hip._info_track_operands(meta(N, T, J, 3), meta(N, T, J, 6), None, vel_weight, accel_weight, huber_px, reweights, max_gap, min_pivot_ratio,
+                             what, dense=False)
+    hip._on_device(what, heatmaps, coord_trans_mat, exc=ValueError)
+    frames = heatmaps.reshape((N * T, V, J, H, W))
+    ctm = None if coord_trans_mat is None else coord_trans_mat.reshape(N * T, V, 4, 4)
+    joints3d, joints2d = decode_joints_3d(frames, cameras, ctm, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
+    track = smooth_trajectory(joints3d.pose.view(N, T, J, 3), None, joints3d.valid.view(N, T, J), lin_weight, 0.0, 0.0, 0, max_gap)
+    information = joint_information(track.pose.detach().reshape(N * T, J, 3), joints2d.maxvals.detach(), cameras, ctm, (H, W), threshold,
+                                    min_det_ratio, camera_calib_file_dir_path)
+    fine = smooth_trajectory_info(joints3d.pose.detach().view(N, T, J, 3), information.info.view(N, T, J, 6), joints3d.valid.view(N, T, J),
+                                  accel_weight, vel_weight, huber_px, reweights, max_gap, min_pivot_ratio)
+    clip = Joints3D(joints3d.pose.view(N, T, J, 3), joints3d.cost.view(N, T, J), joints3d.residual.view(N, T, V, J), joints3d.valid.view(N, T, J))
+    if one:
+        clip, track, fine = (Joints3D(*(t.squeeze(0) for t in clip)), Track3D(*(t.squeeze(0) for t in track)),
+                             InfoTrack3D(*(t.squeeze(0) for t in fine)))
+    return clip, track, fine

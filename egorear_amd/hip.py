@@ -193,6 +193,7 @@ EXPORTS = [
     "egr_peaks_f32", "egr_consensus_f32", "egr_skeleton_fit_f32", "egr_bone_lengths_f32", "egr_skeleton_resize_f32",
     "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32", "egr_rig_refine_f32", "egr_rig_refine_workspace_bytes",
     "egr_ray_track_f32", "egr_ray_track_workspace_bytes",
+    "egr_joint_info_f32", "egr_info_track_f32", "egr_info_track_workspace_bytes",
 ]
 
 
@@ -339,6 +340,10 @@ def _load() -> C.CDLL:
     lib.egr_ray_track_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.egr_ray_track_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, i32, i32, C.c_double, vp, i64, vp, vp, vp,
                                       vp, vp, vp, vp]
+    lib.egr_joint_info_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp]
+    lib.egr_info_track_workspace_bytes.restype = C.c_int64
+    lib.egr_info_track_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.egr_info_track_f32.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, C.c_double, vp, i64, vp, vp, vp, vp, vp, vp]
     lib.egr_coord_l1_f32.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.egr_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
     lib.egr_joint_mha_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp]
@@ -381,7 +386,7 @@ def _load() -> C.CDLL:
         getattr(lib, name)  # fail at import if a symbol is missing
         if name not in ("egr_version", "egr_w6_elems", "egr_stem_w6_bytes", "egr_wh2_elems", "egr_stem_wh2_bytes", "egr_wstream_image_bytes",
                         "egr_linear_wstream_workspace_bytes", "egr_rig_refine_workspace_bytes",
-                        "egr_ray_track_workspace_bytes"):
+                        "egr_ray_track_workspace_bytes", "egr_info_track_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     return lib
 
@@ -1950,6 +1955,96 @@ def ray_track(coords: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm:
             _stream(), flops=N * T * J * (solves * (V * 90.0 + 330.0) + V * 60.0),
             nbytes=N * T * J * (V * (12.0 + 32.0) + solves * (V * 32.0 + 3.0 * 144.0 + 24.0) + V * 40.0 + 38.0))
     return pose, valid, residual, weight, rays, energy
+
+
+INFO_TRACK_SOLVE_SLOTS = 18       # fp64 workspace planes of T * N * J of egr_infotrack.hip: E (9), D^-1 (6), q (3)
+
+
+def _joint_info_operands(points, conf, cams, ctm, sx, sy, threshold, min_det_ratio, what: str, dense: bool = True):
+    """(B, V, J) of a joint-information launch; every shape / dtype / parameter error as ValueError."""
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"egorear_amd.{what}: points must be (B, J, 3), got {tuple(points.shape)}")
+    B, J = int(points.shape[0]), int(points.shape[1])
+    if B < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty points {tuple(points.shape)}")
+    if conf.dim() != 3 or (int(conf.shape[0]), int(conf.shape[2])) != (B, J):
+        raise ValueError(f"egorear_amd.{what}: conf must be ({B}, V, {J}), got {tuple(conf.shape)}")
+    V = int(conf.shape[1])
+    _rig(what, cams, ctm, B, V)
+    if B * J * V >= 1 << 30:
+        raise ValueError(f"egorear_amd.{what}: B * J * V must stay below 2^30, got {tuple(conf.shape)}")
+    _float32(what, (points, "points"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    _positive(what, "the coordinate scales", sx, sy)
+    if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == threshold):
+        raise ValueError(f"egorear_amd.{what}: threshold must be a number, got {threshold!r}")
+    _non_negative(what, "min_det_ratio", min_det_ratio)
+    _contiguous(what, dense, (points, "points"), (conf, "conf"), (cams, "cams"), (ctm, "coord_trans_mat"))
+    return B, V, J
+
+
+def joint_info(points: torch.Tensor, conf: torch.Tensor, cams: torch.Tensor, ctm: Optional[torch.Tensor] = None, sx: float = 1.0,
+               sy: float = 1.0, threshold: float = 0.5, min_det_ratio: float = 1e-6):
+    """points (B,J,3) cm, conf (B,V,J), cams (V,30) = camera.packed_rays(), ctm (B,V,4,4) | None (the syn rig) -> info (B,J,6), views
+    (B,J) u8, sigma (B,J), valid (B,J) u8: egr_joint_info_f32, the 3 x 3 information matrix sum_v conf_v J_v^T J_v of the views'
+    reprojections at every point (include/egorear_hip.h states which views enter and what sigma and valid are)."""
+    B, V, J = _joint_info_operands(points, conf, cams, ctm, sx, sy, threshold, min_det_ratio, "joint_info")
+    _on_device("joint_info", points, conf, cams, ctm)
+    dev = points.device
+    info = torch.empty((B, J, 6), device=dev, dtype=torch.float32)
+    sigma = torch.empty((B, J), device=dev, dtype=torch.float32)
+    views, valid = (torch.empty((B, J), device=dev, dtype=torch.uint8) for _ in range(2))
+    _launch("egr_joint_info_f32", lib.egr_joint_info_f32, _p(points), _p(conf), _p(cams), _p(ctm), B, V, J, float(sx), float(sy),
+            float(threshold), float(min_det_ratio), _p(info), _p(views, torch.uint8), _p(sigma), _p(valid, torch.uint8), _stream(),
+            flops=B * J * (V * 150.0 + 60.0), nbytes=B * J * (V * (4.0 + (64.0 if ctm is not None else 0.0)) + 12.0 + 30.0))
+    return info, views, sigma, valid
+
+
+def _info_track_operands(pose, info, obs, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio, what: str, dense: bool = True):
+    """(N, T, J) of an information-track launch; every shape / dtype / parameter error as ValueError."""
+    if pose.dim() != 4 or pose.shape[-1] != 3:
+        raise ValueError(f"egorear_amd.{what}: pose must be (N, T, J, 3), got {tuple(pose.shape)}")
+    N, T, J = (int(v) for v in pose.shape[:3])
+    if N < 1 or T < 1 or J < 1:
+        raise ValueError(f"egorear_amd.{what}: empty pose {tuple(pose.shape)}")
+    if T > TRAJECTORY_MAX_T:
+        raise ValueError(f"egorear_amd.{what}: at most {TRAJECTORY_MAX_T} frames a clip are supported, got {T}")
+    if tuple(info.shape) != (N, T, J, 6):
+        raise ValueError(f"egorear_amd.{what}: info must be {(N, T, J, 6)}, got {tuple(info.shape)}")
+    if N * T * J * 6 >= 1 << 31:
+        raise ValueError(f"egorear_amd.{what}: N * T * J * 6 must stay below 2^31, got {tuple(pose.shape)}")
+    if obs is not None:
+        _flags(what, obs, (N, T, J), "observed")
+    _float32(what, (pose, "pose"), (info, "info"))
+    _trajectory_parameters(what, vel_weight, accel_weight, huber, reweights, max_gap)
+    if not (isinstance(min_pivot_ratio, (int, float)) and not isinstance(min_pivot_ratio, bool) and 0.0 <= min_pivot_ratio < 1.0):
+        raise ValueError(f"egorear_amd.{what}: min_pivot_ratio must be a number in [0, 1), got {min_pivot_ratio!r}")
+    _contiguous(what, dense, (pose, "pose"), (info, "info"), (obs, "observed"))
+    return N, T, J
+
+
+def info_track(pose: torch.Tensor, info: torch.Tensor, obs: Optional[torch.Tensor] = None, vel_weight: float = 0.0, accel_weight: float = 1.0,
+               huber: float = 0.0, reweights: int = 0, max_gap: int = 8, min_pivot_ratio: float = 1e-10):
+    """pose (N,T,J,3) cm, info (N,T,J,6) = joint_info's matrices, obs (N,T,J) u8 / bool | None (every frame) -> pose_out (N,T,J,3),
+    valid (N,T,J) u8, residual (N,T,J) in coordinate units, weight (N,T,J), energy (N,J): egr_info_track_f32, the clip smoother whose
+    data term is (x - z)^T W (x - z) a frame (include/egorear_hip.h states the energy, the Huber reweighting in pixels, the solvability
+    and the validity rule).  The fp64 workspace is allocated here, like the outputs.  One launch."""
+    N, T, J = _info_track_operands(pose, info, obs, vel_weight, accel_weight, huber, reweights, max_gap, min_pivot_ratio, "info_track")
+    _on_device("info_track", pose, info, obs)
+    if obs is not None:
+        obs = _flags("info_track", obs, (N, T, J), "observed")
+    dev = pose.device
+    nbytes_ws = int(lib.egr_info_track_workspace_bytes(N, T, J))
+    ws = torch.empty((nbytes_ws // 8,), device=dev, dtype=torch.float64)
+    pose_out = torch.empty((N, T, J, 3), device=dev, dtype=torch.float32)
+    valid = torch.empty((N, T, J), device=dev, dtype=torch.uint8)
+    residual, weight = (torch.empty((N, T, J), device=dev, dtype=torch.float32) for _ in range(2))
+    energy = torch.empty((N, J), device=dev, dtype=torch.float32)
+    solves = reweights + 1.0
+    _launch("egr_info_track_f32", lib.egr_info_track_f32, _p(pose), _p(info), _p(obs, torch.uint8), N, T, J, float(vel_weight),
+            float(accel_weight), float(huber), int(reweights), int(max_gap), float(min_pivot_ratio), _p(ws, torch.float64), nbytes_ws,
+            _p(pose_out), _p(valid, torch.uint8), _p(residual), _p(weight), _p(energy), _stream(),
+            flops=N * T * J * (solves * 360.0 + 40.0), nbytes=N * T * J * (solves * (37.0 + 3.0 * 144.0 + 24.0) + 37.0 + 24.0 + 21.0))
+    return pose_out, valid, residual, weight, energy
 
 
 def layernorm(x: torch.Tensor, gamma, beta, res: Optional[torch.Tensor] = None, eps: float = 1e-5, groups: int = 1) -> torch.Tensor:

@@ -726,6 +726,52 @@ int egr_ray_track_f32(const float* coords, const float* conf, const float* cams,
                       float* pose /* N x T x J x 3 */, uint8_t* valid /* N x T x J */, float* residual /* N x T x V x J */,
                       float* weight /* N x T x V x J */, uint8_t* rays /* N x T x J */, float* energy /* N x J */, void* stream);
 
+/* Information-weighted clip smoothing, two entries.
+ * egr_joint_info_f32: the information matrix of a 3-D point under the views that see it.  points (B, J, 3) cm in the device frame,
+ * conf (B, V, J), cams (V, 30) ray records, ctm NULL (the syn rig, each camera on its own) or (B, V, 4, 4) - the extrinsics of
+ * egr_triangulate_f32.  With c_v(p) the coordinates of the point in view v in the units of `coords` everywhere in the decoders (image
+ * pixels / (sx W_img, sy H_img): heat-map pixels for sx = 1 / W) and J_v = d c_v / d p (2 x 3)
+ *   W = sum_v conf_v J_v^T J_v   over the views that enter:
+ * conf >= threshold, conf > 0, conf finite (egr_triangulate_f32's rule), and the point gives a pixel off the optical axis - the
+ * camera-frame point q = R p + t is finite with n = |q_xy| > 0.  A view that does not enter weighs nothing and nothing of it is read
+ * into an output; a point that is not finite gives zeros, views 0, valid 0.  No coordinates are taken: W depends on where the point
+ * is, not on where it was observed.  J_v is analytic: theta = atan2(-q_z, n), rho(theta) and rho'(theta) of the W2C polynomial (Horner).
+ * info (B, J, 6): W in the order (00, 01, 02, 11, 12, 22); views (B, J): the views that entered; valid (B, J): W passes
+ * egr_triangulate_f32's LDL^T test with min_det_ratio; sigma (B, J) = sqrt(trace(W^-1)) where valid - cm of positional standard
+ * deviation per unit of coordinate noise - else 0.  One thread per (frame, joint), fp64 arithmetic on fp32 operands, a fixed order over
+ * the views, no atomics.  EGR_EINVAL: the shapes, scales and min_det_ratio egr_triangulate_f32 refuses, threshold NaN.
+ *
+ * egr_info_track_f32: the clip smoother with one such matrix a frame.  A track is one joint j of one clip n, T frames of observations
+ * z_t = pose[n, t, j] (cm) with W_t = info[n, t, j]; it minimises over x_0..x_{T-1}
+ *   E(x) = sum_t rho(r_t) + vel_weight sum_{t=0}^{T-2} |x_{t+1} - x_t|^2 + accel_weight sum_{t=1}^{T-2} |x_{t+1} - 2 x_t + x_{t-1}|^2,
+ *   r_t = sqrt((x_t - z_t)^T W_t (x_t - z_t))   - the displacement in coordinate units (pixels) -
+ * over the frames that are used: obs != 0 (NULL: every frame), pose and the six entries finite, every diagonal entry >= 0 and the
+ * trace > 0.  Any other frame is a gap that its neighbours fill, and what stands there is never read.  A positive semi-definite W of
+ * rank 2 (one view) is a legitimate frame.  rho is the square, or Huber's function at huber > 0 (in pixels: r_t has the noise's units).
+ *   Plain form: x solves (blockdiag(W_t) + (vel_weight D1^T D1 + accel_weight D2^T D2) (x) I_3) x = (W_t z_t) - egr_ray_track_f32's
+ *   system with G_t = W_t, g_t = W_t z_t, and its elimination (block LDL^T without pivoting, the same code).
+ *   Robust form (huber > 0, reweights = K in 1..16): x(0) the plain solve; x(k+1) solves the plain problem with s_t W_t,
+ *   s_t = min(1, huber / r_t(x(k))); K + 1 solves, always.  E does not increase from one k to the next.
+ *   A track is solvable when (a) it has enough used frames for its penalties - 1 with vel_weight > 0; with vel_weight == 0, 2 where
+ *   T >= 3 and every frame where T <= 2 - and (b) every scalar pivot of the plain solve's elimination exceeds min_pivot_ratio x the
+ *   largest diagonal entry of the track's matrix (a NaN fails).  A track that is not solvable gives 0 in every output.
+ * pose_out (N, T, J, 3): written for every frame of a solvable track; valid (N, T, J): 1 iff the track is solvable and a used frame is
+ * at most max_gap frames away; residual (N, T, J): r_t at the result for used frames, 0 elsewhere; weight (N, T, J): s_t of the last
+ * solve (1 in the plain form), 0 for a gap; energy (N, J): E at the result.  workspace: egr_info_track_workspace_bytes(N, T, J) bytes
+ * = 18 T N J doubles (0 for shapes the entry refuses), contents unspecified before and after.  The parameters are taken as fp32 except
+ * min_pivot_ratio.  One launch: one lane per track, the tracks of a clip in adjacent lanes, every sweep of the K + 1 solves and the
+ * energy pass inside it.  No atomics, a fixed order: the same bits every run, alone or in a batch.  Latency-bound.
+ * EGR_EINVAL: N or J < 1, T outside 1..4096, N*T*J*6 >= 2^31, the penalties, huber, reweights and max_gap as
+ * egr_trajectory_smooth_f32 refuses them, min_pivot_ratio negative, NaN or >= 1; EGR_EWORKSPACE: workspace_bytes too small. */
+int egr_joint_info_f32(const float* points, const float* conf, const float* cams, const float* ctm /* nullable */, int32_t B, int32_t V,
+                       int32_t J, float sx, float sy, float threshold, float min_det_ratio, float* info /* B x J x 6 */,
+                       uint8_t* views /* B x J */, float* sigma /* B x J */, uint8_t* valid /* B x J */, void* stream);
+int64_t egr_info_track_workspace_bytes(int32_t N, int32_t T, int32_t J);
+int egr_info_track_f32(const float* pose, const float* info, const uint8_t* obs /* nullable */, int32_t N, int32_t T, int32_t J,
+                       float vel_weight, float accel_weight, float huber, int32_t reweights, int32_t max_gap, double min_pivot_ratio,
+                       double* workspace, int64_t workspace_bytes, float* pose_out /* N x T x J x 3 */, uint8_t* valid /* N x T x J */,
+                       float* residual /* N x T x J */, float* weight /* N x T x J */, float* energy /* N x J */, void* stream);
+
 /* y = LayerNorm(x (+ res)) * gamma + beta over the last dim c (c <= 1024, c % 64 == 0), eps 1e-5. */
 int egr_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                       int32_t rows, int32_t c, float eps, int32_t rows_per_group /* gamma/beta + (row/rows_per_group)*c; 0 = one group */,
