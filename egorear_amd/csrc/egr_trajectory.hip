@@ -450,3 +450,289 @@ extern "C" int egr_trajectory_smooth_bwd_f32(const float* pose, const float* wei
                        workspace, g_pose, g_weight);
     return egr_launch_status();
 }
+
+// ---- the causal fixed-lag filter of a stream of frames ---------------------------------------------------------------
+// The forward elimination above is a causal recursion: for the prefix problem over the frames 0..t only the last two rows of A carry
+// boundary coefficients (trj_band(s, T) does not depend on T for s <= T - 3), so row t - 2 is final the moment frame t arrives.  A
+// stream's state is the chain after its final rows, the two frames whose rows are not final yet, and a ring of the last `lag` final
+// rows; the arrival of frame t commits row t - 2, takes the two provisional steps of the prefix's boundary rows on a copy of the chain
+// and substitutes back `lag` rows: frame t - lag of the plain solution over 0..t.  With gate = delta > 0 the arriving observation is
+// first weighed against the prediction p_t the earlier frames make for it - the last row's q of the same prefix with w_t = 0, one
+// more elimination step: u_t = w_t min(1, delta / |z_t - p_t|), fixed from then on.
+//
+// One lane per track, the tracks of a stream in adjacent lanes.  The state is fp64, laid out (slot, track) - a wave's accesses at one
+// slot coalesce:
+//   0..10   the chain: d1, d2, e1, f1, f2, y1[3], y2[3]                 (trj_chain<3> after the last final row)
+//   11..15  the older pending frame (t - 1 once t has arrived): u, z[3], frames since the last observed one
+//   16..20  the newer pending frame (t): the same
+//   21      frames seen                      22   observed frames seen, saturating at 2
+//   23 + 10 r ..   row s of the ring, r = s mod lag: e, f, q[3], z[3], u, frames since the last observed one
+// All zeros is the empty stream.  A reset starts slots 0..22 from zero and leaves the ring as it is: a substitution reaches only rows
+// committed since, so the earlier stream's rows are never read (and a reset tensor need not be all zeros).  The band needs min(t, 2) and the distance to the prefix's end only, so no coefficient depends on a
+// stream's length; slot 21 counts exactly up to 2^53 frames.  The C frames of a call run the same per-frame code one after another.
+namespace {
+
+constexpr int TRF_MAX_LAG = 64, TRF_HEAD = 23, TRF_ROW = 10;
+
+struct trf_pend {
+    double u, z[3], since;
+};
+
+struct trf_state {
+    trj_chain<3> ch;
+    trf_pend a, b;           // frames n - 2 and n - 1
+    int64_t n;
+    int seen;
+};
+
+struct trf_args {
+    double lv, la, gate;
+    int lag, max_gap;
+    int64_t tracks;
+};
+
+__device__ inline void trf_load(const double* S, int64_t tr, bool clear, trf_state& st) {
+    double v[TRF_HEAD];
+#pragma unroll
+    for (int i = 0; i < TRF_HEAD; ++i) v[i] = S[i * tr];
+#pragma unroll
+    for (int i = 0; i < TRF_HEAD; ++i) v[i] = clear ? 0.0 : v[i];
+    st.ch.d1 = v[0], st.ch.d2 = v[1], st.ch.e1 = v[2], st.ch.f1 = v[3], st.ch.f2 = v[4];
+    for (int c = 0; c < 3; ++c) st.ch.y1[c] = v[5 + c], st.ch.y2[c] = v[8 + c], st.a.z[c] = v[12 + c], st.b.z[c] = v[17 + c];
+    st.a.u = v[11], st.a.since = v[15], st.b.u = v[16], st.b.since = v[20];
+    st.n = (int64_t)v[21];
+    st.seen = (int)v[22];
+}
+
+__device__ inline void trf_store(double* S, int64_t tr, const trf_state& st) {
+    S[0] = st.ch.d1, S[tr] = st.ch.d2, S[2 * tr] = st.ch.e1, S[3 * tr] = st.ch.f1, S[4 * tr] = st.ch.f2;
+    for (int c = 0; c < 3; ++c) {
+        S[(5 + c) * tr] = st.ch.y1[c];
+        S[(8 + c) * tr] = st.ch.y2[c];
+        S[(12 + c) * tr] = st.a.z[c];
+        S[(17 + c) * tr] = st.b.z[c];
+    }
+    S[11 * tr] = st.a.u, S[15 * tr] = st.a.since, S[16 * tr] = st.b.u, S[20 * tr] = st.b.since;
+    S[21 * tr] = (double)st.n;
+    S[22 * tr] = (double)st.seen;
+}
+
+// Row t of a prefix whose last row is t + to_end: trj_band reads t through (t >= 1), (t >= 2) and T - t only.
+__device__ inline void trf_band(int64_t t, int to_end, const trf_args& p, double& a, double& b, double& c) {
+    const int ts = (int)(t < 2 ? t : 2);
+    trj_band(ts, ts + to_end + 1, p.lv, p.la, a, b, c);
+}
+
+__device__ inline bool trf_solvable(const trf_args& p, int64_t n, int seen) {
+    return p.lv > 0.0 ? seen >= 1 : (n >= 3 ? seen >= 2 : (int64_t)seen == n);
+}
+
+__device__ inline double trf_next(double since) { return since < (double)TRJ_FAR ? since + 1.0 : (double)TRJ_FAR; }
+
+// The two boundary rows n - 2 (st.a) and n - 1 (st.b) of the prefix of n >= 1 frames, on a copy of the chain.  With `gating` the
+// newest frame's weight st.b.u is still its base weight: it is weighed against the prediction first (`seen` counts the frames before it).
+__device__ inline void trf_boundary(trf_state& st, const trf_args& p, bool gating, int seen, double& ea, double* qa, double* qb) {
+    trj_chain<3> pr = st.ch;
+    double a, b, c, e, f;
+    ea = 0.0;
+    qa[0] = qa[1] = qa[2] = 0.0;
+    if (st.n >= 2) {
+        trf_band(st.n - 2, 1, p, a, b, c);
+        const double rhs[3] = {st.a.u * st.a.z[0], st.a.u * st.a.z[1], st.a.u * st.a.z[2]};
+        pr.step(a + st.a.u, b, c, rhs, ea, f, qa);
+    }
+    trf_band(st.n - 1, 0, p, a, b, c);
+    if (gating) {
+        trj_chain<3> g = pr;
+        double pred[3];
+        const double none[3] = {0.0, 0.0, 0.0};
+        g.step(a, b, c, none, e, f, pred);
+        const bool known = p.lv > 0.0 ? seen >= 1 : (st.n >= 3 && seen >= 2);       // trf_solvable of the prefix with w = 0 at its end
+        const double r = trj_dist(pred, st.b.z);
+        st.b.u = (known && st.b.u > 0.0 && r > p.gate) ? st.b.u * (p.gate / r) : st.b.u;
+    }
+    const double rhs[3] = {st.b.u * st.b.z[0], st.b.u * st.b.z[1], st.b.u * st.b.z[2]};
+    pr.step(a + st.b.u, b, c, rhs, e, f, qb);
+}
+
+struct trf_out {
+    float* pose;
+    uint8_t* valid;
+    float* residual;
+    float* weight;
+};
+
+__device__ inline void trf_write(const trf_out& o, int64_t at, bool ok, const double* x, const double* z, double u, double gap, int max_gap) {
+    for (int c = 0; c < 3; ++c) o.pose[at * 3 + c] = ok ? (float)x[c] : 0.0f;
+    o.valid[at] = (ok && gap <= (double)max_gap) ? 1 : 0;
+    o.residual[at] = (ok && u > 0.0) ? (float)trj_dist(x, z) : 0.0f;
+    o.weight[at] = ok ? (float)u : 0.0f;
+}
+
+__device__ inline void trf_blank(const trf_out& o, int64_t at) {
+    o.pose[at * 3] = o.pose[at * 3 + 1] = o.pose[at * 3 + 2] = 0.0f;
+    o.valid[at] = 0;
+    o.residual[at] = o.weight[at] = 0.0f;
+}
+
+// Back-substitution of the prefix of st.n >= 1 frames from its last row down: ALL = false walks lag + 1 rows and writes frame
+// n - 1 - lag at `at` (the caller has checked that it exists); ALL = true walks lag rows and writes each, the last frame at `at`, earlier
+// ones `step` elements before (rows before the stream's start are left to the caller).
+template <bool ALL>
+__device__ inline void trf_substitute(const trf_state& st, const double* S, const trf_args& p, double ea, const double* qa, const double* qb,
+                                      const trf_out& o, int64_t at, int64_t step) {
+    const int64_t tr = p.tracks;
+    const bool ok = trf_solvable(p, st.n, st.seen);
+    const int last = ALL ? p.lag - 1 : p.lag;
+    double x1[3] = {0.0, 0.0, 0.0}, x2[3] = {0.0, 0.0, 0.0};
+    double until = (double)TRJ_FAR;
+    int r = p.lag > 0 ? (int)((st.n + (int64_t)p.lag - 3) % p.lag) : 0;             // row n - 3 of the ring (read where n >= 3 only)
+    for (int i = 0; i <= last; ++i) {
+        if (st.n - 1 - i < 0) break;
+        const bool emit = ALL || i == last;
+        double e, f, q[3], z[3] = {0.0, 0.0, 0.0}, u, since = 0.0;
+        if (i == 0) {
+            e = f = 0.0;
+            u = st.b.u, since = st.b.since;
+            for (int c = 0; c < 3; ++c) q[c] = qb[c], z[c] = st.b.z[c];
+        } else if (i == 1) {
+            e = ea, f = 0.0;
+            u = st.a.u, since = st.a.since;
+            for (int c = 0; c < 3; ++c) q[c] = qa[c], z[c] = st.a.z[c];
+        } else {
+            const double* R = S + (int64_t)(TRF_HEAD + TRF_ROW * r) * tr;
+            e = R[0], f = R[tr], u = R[8 * tr];
+            for (int c = 0; c < 3; ++c) q[c] = R[(2 + c) * tr];
+            if (emit) {
+                for (int c = 0; c < 3; ++c) z[c] = R[(5 + c) * tr];
+                since = R[9 * tr];
+            }
+            r = r == 0 ? p.lag - 1 : r - 1;
+        }
+        double x[3];
+        for (int c = 0; c < 3; ++c) x[c] = q[c] - e * x1[c] - f * x2[c];
+        until = u > 0.0 ? 0.0 : trf_next(until);
+        if (emit) trf_write(o, at - (ALL ? (int64_t)i * step : 0), ok, x, z, u, since < until ? since : until, p.max_gap);
+        for (int c = 0; c < 3; ++c) {
+            x2[c] = x1[c];
+            x1[c] = x[c];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void trajectory_filter_kernel(trj_args in, trf_args p, const uint8_t* reset, double* state, trf_out o,
+                                                               int64_t* frame) {
+    const int64_t k = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (k >= p.tracks) return;
+    const int C = in.T, J = in.J;
+    const int64_t n = k / J, j = k - n * J;
+    const int64_t base = n * C * J + j;                  // the track's frame c of this call is element base + c * J
+    double* const S = state + k;
+    // (no branch around the optional operand's load, as trj_fetch: without a reset the load goes to the pose and is selected away)
+    const uint8_t flag = *(reset ? reset + n : (const uint8_t*)in.pose);
+    trf_state st;
+    trf_load(S, p.tracks, reset && flag != 0, st);
+    trj_raw cur, nxt;
+    trj_fetch(in, base, cur);
+    for (int c = 0; c < C; ++c) {
+        trj_fetch(in, base + (int64_t)trj_min(c + 1, C - 1) * J, nxt);
+        trj_frame f;
+        trj_decode(cur, f);
+        const int64_t t = st.n;
+        if (t >= 2) {                                    // row t - 2 is final: interior coefficients
+            double a, b, cc, e, ff, q[3];
+            trf_band(t - 2, 2, p, a, b, cc);
+            const double rhs[3] = {st.a.u * st.a.z[0], st.a.u * st.a.z[1], st.a.u * st.a.z[2]};
+            st.ch.step(a + st.a.u, b, cc, rhs, e, ff, q);
+            if (p.lag > 0) {
+                double* R = S + (int64_t)(TRF_HEAD + TRF_ROW * (int)((t - 2) % p.lag)) * p.tracks;
+                R[0] = e, R[p.tracks] = ff, R[8 * p.tracks] = st.a.u, R[9 * p.tracks] = st.a.since;
+                for (int i = 0; i < 3; ++i) R[(2 + i) * p.tracks] = q[i], R[(5 + i) * p.tracks] = st.a.z[i];
+            }
+        }
+        const int before = st.seen;
+        st.a = st.b;
+        st.b.u = f.w;
+        for (int i = 0; i < 3; ++i) st.b.z[i] = f.z[i];
+        st.b.since = f.w > 0.0 ? 0.0 : (t == 0 ? (double)TRJ_FAR : trf_next(st.a.since));
+        st.n = t + 1;
+        st.seen = trj_min(before + (f.w > 0.0 ? 1 : 0), 2);
+        double ea, qa[3], qb[3];
+        trf_boundary(st, p, p.gate > 0.0, before, ea, qa, qb);
+        const int64_t at = base + (int64_t)c * J;
+        if (t >= p.lag) trf_substitute<false>(st, S, p, ea, qa, qb, o, at, 0);
+        else trf_blank(o, at);
+        if (j == 0) frame[n * C + c] = t >= p.lag ? t - p.lag : -1;
+        cur = nxt;
+    }
+    trf_store(S, p.tracks, st);
+}
+
+__global__ __launch_bounds__(64) void trajectory_filter_tail_kernel(trf_args p, int J, const double* state, trf_out o, int64_t* frame) {
+    const int64_t k = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (k >= p.tracks) return;
+    const int64_t n = k / J, j = k - n * J;
+    const double* const S = state + k;
+    trf_state st;
+    trf_load(S, p.tracks, false, st);
+    const int64_t end = (n * p.lag + (p.lag - 1)) * J + j;      // the last row: frame st.n - 1
+    if (st.n >= 1) {
+        double ea, qa[3], qb[3];
+        trf_boundary(st, p, false, 0, ea, qa, qb);
+        trf_substitute<true>(st, S, p, ea, qa, qb, o, end, J);
+    }
+    for (int i = 0; i < p.lag; ++i) {                    // row lag - 1 - i is frame st.n - 1 - i
+        if (st.n - 1 - i < 0) trf_blank(o, end - (int64_t)i * J);
+        if (j == 0) frame[n * p.lag + (p.lag - 1 - i)] = st.n - 1 - i >= 0 ? st.n - 1 - i : -1;
+    }
+}
+
+inline bool trf_shape_ok(int32_t N, int32_t C, int32_t J, int32_t lag, float lv, float la, int32_t max_gap) {
+    if (lag < 0 || lag > TRF_MAX_LAG || max_gap < 0) return false;
+    if (!trj_shape_ok(N, C, J, lv, la)) return false;
+    return (int64_t)N * J * (TRF_HEAD + TRF_ROW * lag) < ((int64_t)1 << 31);
+}
+
+inline trf_args trf_pack(int32_t N, int32_t J, int32_t lag, float lv, float la, float gate, int32_t max_gap) {
+    trf_args p;
+    p.lv = (double)lv;
+    p.la = (double)la;
+    p.gate = (double)gate;
+    p.lag = lag;
+    p.max_gap = max_gap;
+    p.tracks = (int64_t)N * J;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int64_t egr_trajectory_filter_state_slots(int32_t lag) {
+    return lag < 0 || lag > TRF_MAX_LAG ? (int64_t)EGR_EINVAL : (int64_t)(TRF_HEAD + TRF_ROW * lag);
+}
+
+extern "C" int egr_trajectory_filter_f32(const float* pose, const float* weight, const uint8_t* obs, const uint8_t* reset, double* state,
+                                         int32_t N, int32_t C, int32_t J, int32_t lag, float vel_weight, float accel_weight, float gate,
+                                         int32_t max_gap, float* pose_out, uint8_t* valid, float* residual, float* weight_out, int64_t* frame,
+                                         void* stream) {
+    if (!pose || !state || !pose_out || !valid || !residual || !weight_out || !frame) return EGR_ENULL;
+    if (!trf_shape_ok(N, C, J, lag, vel_weight, accel_weight, max_gap) || !trj_number(gate)) return EGR_EINVAL;
+    const trj_args in = trj_pack(pose, weight, obs, N, C, J, vel_weight, accel_weight, 0.0f, 0, max_gap);
+    const trf_args p = trf_pack(N, J, lag, vel_weight, accel_weight, gate, max_gap);
+    const trf_out o = {pose_out, valid, residual, weight_out};
+    hipLaunchKernelGGL(trajectory_filter_kernel, dim3((unsigned)((p.tracks + 63) / 64)), dim3(64), 0, (hipStream_t)stream, in, p, reset, state,
+                       o, frame);
+    return egr_launch_status();
+}
+
+extern "C" int egr_trajectory_filter_tail_f32(const double* state, int32_t N, int32_t J, int32_t lag, float vel_weight, float accel_weight,
+                                              int32_t max_gap, float* pose_out, uint8_t* valid, float* residual, float* weight_out,
+                                              int64_t* frame, void* stream) {
+    if (!state || !pose_out || !valid || !residual || !weight_out || !frame) return EGR_ENULL;
+    if (!trf_shape_ok(N, 1, J, lag, vel_weight, accel_weight, max_gap)) return EGR_EINVAL;
+    if (lag == 0) return 0;                              // no rows
+    const trf_args p = trf_pack(N, J, lag, vel_weight, accel_weight, 0.0f, max_gap);
+    const trf_out o = {pose_out, valid, residual, weight_out};
+    hipLaunchKernelGGL(trajectory_filter_tail_kernel, dim3((unsigned)((p.tracks + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p, J, state, o,
+                       frame);
+    return egr_launch_status();
+}

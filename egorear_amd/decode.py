@@ -54,6 +54,13 @@ frame.  `decode_clip_3d_rays` chains heat maps of a clip -> Joints2D -> RayTrack
 the scalar weight, on `egr_info_track_f32`, operator `egorear_amd::info_track` (DESIGN.md 5v) - the range, which a near-parallel pair
 measures badly, is smoothed hard and the directions across it barely.  Neither is differentiable.  `decode_clip_3d_info` chains heat
 maps of a clip -> Joints3D -> Track3D (the linearisation track) -> Information3D at that track -> InfoTrack3D, five launches.
+
+`filter_trajectory` is `smooth_trajectory` for a live stream: a causal filter with a fixed lag on `egr_trajectory_filter_f32` /
+`egr_trajectory_filter_tail_f32` (DESIGN.md 5w), operators `egorear_amd::trajectory_filter` (it mutates its state) and
+`egorear_amd::trajectory_filter_tail` - every arriving frame gives frame t - lag of the plain track over the frames seen so far, at a
+cost that does not grow with the stream; a gate down-weights an observation far from what the earlier frames predict.
+`new_track_filter` makes the state, `filter_tail` reads the frames no step has described yet, `decode_stream_3d` chains heat maps ->
+Joints3D -> TrackStep, three launches that one captured graph replays per frame.  Not differentiable.
 """
 from __future__ import annotations
 
@@ -902,6 +909,177 @@ def decode_clip_3d(heatmaps: torch.Tensor, cameras: Union[str, Sequence], coord_
     if one:
         clip, track = Joints3D(*(t.squeeze(0) for t in clip)), Track3D(*(t.squeeze(0) for t in track))
     return clip, track
+
+
+# ---- causal fixed-lag filtering of a stream ------------------------------------------------------------------------------------------
+
+@torch.library.custom_op("egorear_amd::trajectory_filter", mutates_args=("state",), device_types="cuda")
+def trajectory_filter_op(state: torch.Tensor, pose: torch.Tensor, weight: Optional[torch.Tensor], obs: Optional[torch.Tensor],
+                         reset: Optional[torch.Tensor], lag: int, vel_weight: float, accel_weight: float, gate: float, max_gap: int
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pose_out (N, C, J, 3) cm, valid (N, C, J) uint8, residual (N, C, J) cm, weight_out (N, C, J), frame (N, C) int64) of the next C
+    frames pose (N, C, J, 3) of N streams, weight / obs (N, C, J) or None, reset (N,) uint8 or None; `state` (slots, N * J) float64 is
+    updated in place: egr_trajectory_filter_f32.  No output is differentiable."""
+    hip._filter_operands(state, pose, weight, obs, reset, lag, vel_weight, accel_weight, gate, max_gap, "decode.trajectory_filter", dense=False)
+    return hip.trajectory_filter(state, _c(pose), _c(weight), _c(obs), _c(reset), lag, vel_weight, accel_weight, gate, max_gap)
+
+
+def _filter_fake_outputs(like, N, R, J):
+    new = like.new_empty
+    return (new((N, R, J, 3), dtype=torch.float32), new((N, R, J), dtype=torch.uint8), new((N, R, J), dtype=torch.float32),
+            new((N, R, J), dtype=torch.float32), new((N, R), dtype=torch.int64))
+
+
+@trajectory_filter_op.register_fake
+def _trajectory_filter_fake(state, pose, weight, obs, reset, lag, vel_weight, accel_weight, gate, max_gap):
+    N, C, J = hip._filter_operands(state, pose, weight, obs, reset, lag, vel_weight, accel_weight, gate, max_gap, "decode.trajectory_filter",
+                                   dense=False)
+    return _filter_fake_outputs(pose, N, C, J)
+
+
+@torch.library.custom_op("egorear_amd::trajectory_filter_tail", mutates_args=(), device_types="cuda")
+def trajectory_filter_tail_op(state: torch.Tensor, N: int, J: int, lag: int, vel_weight: float, accel_weight: float, max_gap: int
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The five outputs of trajectory_filter for the last `lag` frames of the streams so far, (N, lag, J, ...): egr_trajectory_filter_tail_f32.
+    The state is read only."""
+    return hip.trajectory_filter_tail(state, N, J, lag, vel_weight, accel_weight, max_gap)
+
+
+@trajectory_filter_tail_op.register_fake
+def _trajectory_filter_tail_fake(state, N, J, lag, vel_weight, accel_weight, max_gap):
+    slots = hip._filter_parameters("decode.trajectory_filter_tail", N, J, lag, vel_weight, accel_weight, 0.0, max_gap)
+    hip._filter_state("decode.trajectory_filter_tail", state, N, J, slots)
+    return _filter_fake_outputs(state, N, lag, J)
+
+
+# Not differentiable, as consensus_op: the tail by the same registration; the step mutates its state, and an operator that is not
+# functional takes no autograd formula - `filter_trajectory` hands it detached operands instead.  (A direct call of the operator with
+# operands that require a gradient is not refused at the call: it fails at backward.)
+trajectory_filter_tail_op.register_autograd(_nograd_autograd, setup_context=_nograd_setup_context)
+
+
+class TrackFilterState(NamedTuple):
+    tensor: torch.Tensor     # (slots, N * J) float64 on the device, updated in place by every step (include/egorear_hip.h has the layout)
+    N: int                   # streams
+    J: int                   # joints of a stream
+    lag: int                 # frames an output lies behind the arriving frame
+    accel_weight: float
+    vel_weight: float
+    gate_cm: float           # 0: no gate
+    max_gap: int
+
+
+class TrackStep(NamedTuple):
+    pose: torch.Tensor       # (N, C, J, 3) cm: stream frame `frame` of the track over the frames seen so far; 0 where that is not solvable
+    valid: torch.Tensor      # (N, C, J) bool: solvable and an observed frame among those seen is at most max_gap frames away
+    residual: torch.Tensor   # (N, C, J) cm: |pose - observation| if that frame was observed, else 0
+    weight: torch.Tensor     # (N, C, J) the weight that frame's observation was given: the base weight times the gate's factor
+    frame: torch.Tensor      # (N, C) int64: the stream frame a row describes; -1 (and zeros) where there is none yet
+
+
+def _filter_parameters(what, accel_weight, vel_weight, gate_cm, max_gap):
+    try:
+        return float(vel_weight), float(accel_weight), float(gate_cm), max_gap
+    except (TypeError, ValueError):
+        raise ValueError(f"egorear_amd.{what}: accel_weight, vel_weight and gate_cm must be numbers, got {accel_weight!r}, {vel_weight!r}, "
+                         f"{gate_cm!r}") from None
+
+
+def new_track_filter(N: int, J: int, lag: int, device, accel_weight: float = 10.0, vel_weight: float = 0.0, gate_cm: float = 0.0,
+                     max_gap: int = 8) -> TrackFilterState:
+    """The empty state of N streams of J joints for `filter_trajectory` / `decode_stream_3d`: outputs lie `lag` (0..64) frames behind
+    the arriving frame; the penalties and `max_gap` are `smooth_trajectory`'s; with gate_cm > 0 an arriving observation farther than
+    that from what the earlier frames predict for it is down-weighted by Huber's factor."""
+    what = "decode.new_track_filter"
+    vel_weight, accel_weight, gate_cm, max_gap = _filter_parameters(what, accel_weight, vel_weight, gate_cm, max_gap)
+    hip._filter_parameters(what, N, J, lag, vel_weight, accel_weight, gate_cm, max_gap)
+    if torch.device(device).type not in ("cuda", "meta"):
+        raise ValueError(f"egorear_amd.{what}: no CPU path - the state must live on the HIP device")
+    return TrackFilterState(hip.trajectory_filter_state(N, J, lag, device), N, J, lag, accel_weight, vel_weight, gate_cm, max_gap)
+
+
+def _filter_state(what: str, state) -> Tuple[float, float, float, int]:
+    if not isinstance(state, TrackFilterState) or not isinstance(state.tensor, torch.Tensor):
+        raise ValueError(f"egorear_amd.{what}: state must be a TrackFilterState (new_track_filter), got {type(state).__name__}")
+    vel_weight, accel_weight, gate_cm, max_gap = _filter_parameters(what, state.accel_weight, state.vel_weight, state.gate_cm, state.max_gap)
+    slots = hip._filter_parameters(what, state.N, state.J, state.lag, vel_weight, accel_weight, gate_cm, max_gap)
+    hip._filter_state(what, state.tensor, state.N, state.J, slots)
+    return vel_weight, accel_weight, gate_cm, max_gap
+
+
+def filter_trajectory(state: TrackFilterState, pose: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                      observed: Optional[torch.Tensor] = None, reset: Optional[torch.Tensor] = None) -> TrackStep:
+    """The next frames of the streams of `state`: pose (N, C, J, 3) cm - or (N, J, 3), one frame - with weight (N, C, J) (None: 1),
+    observed (N, C, J) bool / uint8 (None: every frame; `Joints3D.valid` plugs in) and reset (N,) bool / uint8 (a stream so marked
+    starts anew with this call's first frame) -> TrackStep(pose, valid, residual, weight, frame).  The causal, fixed-lag form of
+    `smooth_trajectory`: row c is frame t - lag of the track that `smooth_trajectory`'s plain form gives over the frames 0..t seen so
+    far, t the frame arriving in row c - every frame costs the same, however long the stream.  With the state's gate_cm > 0 an
+    observation's weight is first multiplied by min(1, gate_cm / its distance from the prediction of the earlier frames).  The state is
+    updated in place; the result does not depend on how a stream is cut into calls.  One launch; nothing is differentiable."""
+    what = "decode.filter_trajectory"
+    vel_weight, accel_weight, gate_cm, max_gap = _filter_state(what, state)
+    one = pose.dim() == 3
+    if one:
+        pose = pose.unsqueeze(1)
+        weight = None if weight is None else weight.unsqueeze(1)
+        observed = None if observed is None else observed.unsqueeze(1)
+    if observed is not None:
+        observed = _as_flags(observed)
+    if reset is not None:
+        reset = _as_flags(reset)
+    N, _, J = hip._filter_operands(state.tensor, pose, weight, observed, reset, state.lag, vel_weight, accel_weight, gate_cm, max_gap, what,
+                                   dense=False)
+    if (N, J) != (state.N, state.J):
+        raise ValueError(f"egorear_amd.{what}: the state was made for {state.N} streams of {state.J} joints, got pose {tuple(pose.shape)}")
+    hip._on_device(what, state.tensor, pose, weight, observed, reset, exc=ValueError)
+    out, valid, residual, used, frame = trajectory_filter_op(state.tensor, pose.detach(), None if weight is None else weight.detach(), observed,
+                                                             reset, state.lag, vel_weight, accel_weight, gate_cm, max_gap)
+    step = TrackStep(out, valid.view(torch.bool), residual, used, frame)
+    return TrackStep(*(t.squeeze(1) for t in step)) if one else step
+
+
+def filter_tail(state: TrackFilterState) -> TrackStep:
+    """The last `lag` frames of the streams so far, which no step has described yet, as TrackStep with rows (N, lag, J, ...): the frames
+    T - lag .. T - 1 of the track over all T frames seen (a row before the stream's start: frame -1 and zeros).  At the end of a stream
+    it completes the output; at any time its last row is the causal estimate of the present.  The state is not modified.  One launch."""
+    what = "decode.filter_tail"
+    vel_weight, accel_weight, _, max_gap = _filter_state(what, state)
+    hip._on_device(what, state.tensor, exc=ValueError)
+    out, valid, residual, used, frame = trajectory_filter_tail_op(state.tensor, state.N, state.J, state.lag, vel_weight, accel_weight, max_gap)
+    return TrackStep(out, valid.view(torch.bool), residual, used, frame)
+
+
+def decode_stream_3d(state: TrackFilterState, heatmaps: torch.Tensor, cameras: Union[str, Sequence],
+                     coord_trans_mat: Optional[torch.Tensor] = None, beta: float = 100.0, threshold: float = 0.5, min_det_ratio: float = 1e-6,
+                     camera_calib_file_dir_path: Optional[str] = None) -> Tuple[Joints3D, TrackStep]:
+    """heatmaps (N, C, V, J, H, W) - or (N, V, J, H, W), one frame - -> (Joints3D, TrackStep): `decode_joints_3d` on the N * C frames, then
+    `filter_trajectory` of its pose with observed = its valid flags - three launches with nothing between them, bit-identical to calling
+    the pieces, and no host value takes part: the call can be captured into one graph and replayed for every frame.  `coord_trans_mat`
+    is (N, C, V, 4, 4) ((N, V, 4, 4) for one frame) or None.  Joints3D comes in the call's shape, (N, C, J, ...) or (N, J, ...)."""
+    what = "decode.decode_stream_3d"
+    _filter_state(what, state)
+    one = heatmaps.dim() == 5
+    if one:
+        heatmaps = heatmaps.unsqueeze(1)
+        coord_trans_mat = None if coord_trans_mat is None else coord_trans_mat.unsqueeze(1)
+    if heatmaps.dim() != 6 or not 2 <= heatmaps.shape[2] <= 4:
+        raise ValueError(f"egorear_amd.{what}: heat maps must be (N, C, V, J, H, W) or (N, V, J, H, W) with 2 to 4 views, got "
+                         f"{tuple(heatmaps.shape)}")
+    N, C, V, J = (int(v) for v in heatmaps.shape[:4])
+    if (N, J) != (state.N, state.J):
+        raise ValueError(f"egorear_amd.{what}: the state was made for {state.N} streams of {state.J} joints, got heat maps "
+                         f"{tuple(heatmaps.shape)}")
+    if coord_trans_mat is not None and tuple(coord_trans_mat.shape) != (N, C, V, 4, 4):
+        raise ValueError(f"egorear_amd.{what}: coord_trans_mat must be {(N, C, V, 4, 4)}, got {tuple(coord_trans_mat.shape)}")
+    hip._on_device(what, state.tensor, heatmaps, coord_trans_mat, exc=ValueError)
+    frames = heatmaps.reshape((N * C,) + tuple(heatmaps.shape[2:]))
+    ctm = None if coord_trans_mat is None else coord_trans_mat.reshape(N * C, V, 4, 4)
+    joints3d, _ = decode_joints_3d(frames, cameras, ctm, beta, threshold, min_det_ratio, camera_calib_file_dir_path)
+    step = filter_trajectory(state, joints3d.pose.view(N, C, J, 3), None, joints3d.valid.view(N, C, J))
+    seen = Joints3D(joints3d.pose.view(N, C, J, 3), joints3d.cost.view(N, C, J), joints3d.residual.view(N, C, V, J), joints3d.valid.view(N, C, J))
+    if one:
+        seen, step = Joints3D(*(t.squeeze(1) for t in seen)), TrackStep(*(t.squeeze(1) for t in step))
+    return seen, step
 
 
 # ---- rig self-calibration ------------------------------------------------------------------------------------------------------------

@@ -194,6 +194,7 @@ EXPORTS = [
     "egr_trajectory_smooth_f32", "egr_trajectory_smooth_bwd_f32", "egr_rig_refine_f32", "egr_rig_refine_workspace_bytes",
     "egr_ray_track_f32", "egr_ray_track_workspace_bytes",
     "egr_joint_info_f32", "egr_info_track_f32", "egr_info_track_workspace_bytes",
+    "egr_trajectory_filter_state_slots", "egr_trajectory_filter_f32", "egr_trajectory_filter_tail_f32",
 ]
 
 
@@ -332,6 +333,10 @@ def _load() -> C.CDLL:
     lib.egr_skeleton_resize_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.egr_trajectory_smooth_f32.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.egr_trajectory_smooth_bwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
+    lib.egr_trajectory_filter_state_slots.restype = C.c_int64
+    lib.egr_trajectory_filter_state_slots.argtypes = [i32]
+    lib.egr_trajectory_filter_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp]
+    lib.egr_trajectory_filter_tail_f32.argtypes = [vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp]
     lib.egr_rig_refine_workspace_bytes.restype = C.c_int64
     lib.egr_rig_refine_workspace_bytes.argtypes = [i32, i32, i32]
     lib.egr_rig_refine_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, i32, f32, i32, vp, i64, vp, vp, vp, vp, vp, vp,
@@ -1894,6 +1899,102 @@ def trajectory_smooth_bwd(pose: torch.Tensor, weight: Optional[torch.Tensor], ob
             float(vel_weight), float(accel_weight), _p(ws, torch.float64), _p(g_in), _p(g_weight), _stream(), flops=N * T * J * 2.0 * 70.0,
             nbytes=N * T * J * (2.0 * 64.0 + 2.0 * 17.0 + 12.0 + 16.0))
     return g_in, g_weight
+
+
+TRAJECTORY_FILTER_MAX_LAG = 64
+TRAJECTORY_FILTER_HEAD_SLOTS, TRAJECTORY_FILTER_ROW_SLOTS = 23, 10      # fp64 state planes of N * J: the chain, two frames, two counts; a ring row
+
+
+def trajectory_filter_state_slots(lag: int) -> int:
+    if not _int_in(lag, 0, TRAJECTORY_FILTER_MAX_LAG):
+        raise ValueError(f"egorear_amd.trajectory_filter: lag must be an integer in 0..{TRAJECTORY_FILTER_MAX_LAG}, got {lag!r}")
+    return TRAJECTORY_FILTER_HEAD_SLOTS + TRAJECTORY_FILTER_ROW_SLOTS * lag
+
+
+def _filter_parameters(what: str, N, J, lag, vel_weight, accel_weight, gate, max_gap) -> int:
+    """The slot count of a filter state for N streams of J joints; every parameter error as ValueError."""
+    if not (_int_in(N, 1, (1 << 31) - 1) and _int_in(J, 1, (1 << 31) - 1)):
+        raise ValueError(f"egorear_amd.{what}: N and J must be positive integers, got {N!r}, {J!r}")
+    if not _int_in(lag, 0, TRAJECTORY_FILTER_MAX_LAG):
+        raise ValueError(f"egorear_amd.{what}: lag must be an integer in 0..{TRAJECTORY_FILTER_MAX_LAG}, got {lag!r}")
+    _trajectory_parameters(what, vel_weight, accel_weight, 0.0, 0, max_gap)
+    _non_negative(what, "gate", gate)
+    slots = trajectory_filter_state_slots(lag)
+    if N * J * slots >= 1 << 31:
+        raise ValueError(f"egorear_amd.{what}: N * J * slots must stay below 2^31, got N {N}, J {J}, {slots} slots")
+    return slots
+
+
+def _filter_state(what: str, state, N: int, J: int, slots: int):
+    if state.dtype != torch.float64 or tuple(state.shape) != (slots, N * J):
+        raise ValueError(f"egorear_amd.{what}: state must be a float64 {(slots, N * J)} (trajectory_filter_state), got {state.dtype} "
+                         f"{tuple(state.shape)}")
+    if not state.is_contiguous():                        # (updated in place: a copy would not do, whoever calls)
+        raise ValueError(f"egorear_amd.{what}: state must be contiguous")
+
+
+def _filter_operands(state, pose, weight, obs, reset, lag, vel_weight, accel_weight, gate, max_gap, what: str, dense: bool = True):
+    """(N, C, J) of a filter launch; every shape / dtype / parameter error as ValueError."""
+    N, C, J = _trajectory_operands(pose, weight, obs, vel_weight, accel_weight, 0.0, 0, max_gap, what, dense=dense)
+    slots = _filter_parameters(what, N, J, lag, vel_weight, accel_weight, gate, max_gap)
+    _filter_state(what, state, N, J, slots)
+    if reset is not None:
+        _flags(what, reset, (N,), "reset")
+        _contiguous(what, dense, (reset, "reset"))
+    return N, C, J
+
+
+def trajectory_filter_state(N: int, J: int, lag: int, device) -> torch.Tensor:
+    """The empty state of N streams of J joints at `lag`: zeros (slots, N * J) float64 (include/egorear_hip.h has the layout)."""
+    slots = _filter_parameters("trajectory_filter_state", N, J, lag, 0.0, 1.0, 0.0, 0)
+    if torch.device(device).type not in ("cuda", "meta"):
+        raise ValueError("egorear_amd.trajectory_filter_state: no CPU path - the state lives on the HIP device")
+    return torch.zeros((slots, N * J), device=device, dtype=torch.float64)
+
+
+def _filter_outputs(N: int, R: int, J: int, dev):
+    pose_out = torch.empty((N, R, J, 3), device=dev, dtype=torch.float32)
+    valid = torch.empty((N, R, J), device=dev, dtype=torch.uint8)
+    residual, weight_out = (torch.empty((N, R, J), device=dev, dtype=torch.float32) for _ in range(2))
+    frame = torch.empty((N, R), device=dev, dtype=torch.int64)
+    return pose_out, valid, residual, weight_out, frame
+
+
+def trajectory_filter(state: torch.Tensor, pose: torch.Tensor, weight: Optional[torch.Tensor] = None, obs: Optional[torch.Tensor] = None,
+                      reset: Optional[torch.Tensor] = None, lag: int = 0, vel_weight: float = 0.0, accel_weight: float = 10.0,
+                      gate: float = 0.0, max_gap: int = 8):
+    """state (slots, N*J) f64, updated in place; pose (N,C,J,3) cm: the next C frames of N streams; weight (N,C,J) | None, obs (N,C,J) u8 /
+    bool | None, reset (N,) u8 / bool | None -> pose_out (N,C,J,3), valid (N,C,J) u8, residual, weight_out (N,C,J), frame (N,C) int64:
+    egr_trajectory_filter_f32, the causal fixed-lag form of trajectory_smooth - row c describes stream frame `frame[n, c]`, `lag` frames
+    behind the arriving one (-1 and zeros before the stream is that long)."""
+    N, C, J = _filter_operands(state, pose, weight, obs, reset, lag, vel_weight, accel_weight, gate, max_gap, "trajectory_filter")
+    _on_device("trajectory_filter", state, pose, weight, obs, reset)
+    if obs is not None:
+        obs = _flags("trajectory_filter", obs, (N, C, J), "observed")
+    if reset is not None:
+        reset = _flags("trajectory_filter", reset, (N,), "reset")
+    out = _filter_outputs(N, C, J, pose.device)
+    _launch("egr_trajectory_filter_f32", lib.egr_trajectory_filter_f32, _p(pose), _p(weight), _p(obs, torch.uint8), _p(reset, torch.uint8),
+            _p(state, torch.float64), N, C, J, int(lag), float(vel_weight), float(accel_weight), float(gate), int(max_gap), _p(out[0]),
+            _p(out[1], torch.uint8), _p(out[2]), _p(out[3]), _p(out[4], torch.int64), _stream(), flops=N * C * J * (160.0 + 20.0 * lag),
+            nbytes=N * J * (2.0 * 8.0 * TRAJECTORY_FILTER_HEAD_SLOTS + C * (17.0 + 21.0 + 80.0 + 48.0 * lag)))
+    return out
+
+
+def trajectory_filter_tail(state: torch.Tensor, N: int, J: int, lag: int, vel_weight: float = 0.0, accel_weight: float = 10.0,
+                           max_gap: int = 8):
+    """state (slots, N*J) f64, read only -> pose_out (N,lag,J,3), valid (N,lag,J) u8, residual, weight_out (N,lag,J), frame (N,lag) int64:
+    egr_trajectory_filter_tail_f32, the last `lag` frames of the stream so far, which no arrival has described yet (rows before the
+    stream's start: -1 and zeros).  The last row is the causal estimate of the present."""
+    slots = _filter_parameters("trajectory_filter_tail", N, J, lag, vel_weight, accel_weight, 0.0, max_gap)
+    _filter_state("trajectory_filter_tail", state, N, J, slots)
+    _on_device("trajectory_filter_tail", state)
+    out = _filter_outputs(N, lag, J, state.device)
+    if lag > 0:
+        _launch("egr_trajectory_filter_tail_f32", lib.egr_trajectory_filter_tail_f32, _p(state, torch.float64), N, J, int(lag),
+                float(vel_weight), float(accel_weight), int(max_gap), _p(out[0]), _p(out[1], torch.uint8), _p(out[2]), _p(out[3]),
+                _p(out[4], torch.int64), _stream(), flops=N * J * (80.0 + 20.0 * lag), nbytes=N * J * lag * (80.0 + 21.0))
+    return out
 
 
 RAY_TRACK_RAY_SLOTS, RAY_TRACK_SOLVE_SLOTS = 4, 18    # fp64 workspace planes of T * N * J: d[3], w a view; E (9), D^-1 (6), q (3)

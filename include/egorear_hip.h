@@ -654,6 +654,41 @@ int egr_trajectory_smooth_bwd_f32(const float* pose, const float* weight /* null
                                   float accel_weight, double* workspace /* 8 x T x N x J */, float* g_pose /* N x T x J x 3 */,
                                   float* g_weight /* N x T x J, nullable */, void* stream);
 
+/* Causal fixed-lag filter of streamed 3-D joints: egr_trajectory_smooth_f32's plain form, one frame at a time.  A stream
+ * is one joint's observations z_0, z_1, ... with the base weights w_t above.  The used weights are u_t = w_t, or with gate = delta > 0
+ *   u_t = w_t min(1, delta / |z_t - p_t|),  p_t = frame t of the plain solution over the frames 0..t with the weights u_0..u_{t-1}, 0,
+ * wherever that system is solvable (else u_t = w_t); a weight is fixed once assigned.  x^(t) is the plain solution over the frames 0..t
+ * with the weights u (zeros where that prefix is not solvable, by the rule above with T = t + 1).  The arrival of frame t describes stream
+ * frame t - lag: pose x^(t)_{t-lag}; valid iff the prefix is solvable and the nearest observed frame within 0..t is at most max_gap
+ * away; residual |x - z| there if observed, else 0; weight u there; frame = t - lag.  While t < lag the row is zeros with frame -1.
+ * The C frames pose[n, c] of a call arrive one after another; outputs and state do not depend on how a stream is cut into calls.
+ * reset[n] != 0 empties stream n before the call's first frame: slots 0..22 start from zero; the ring rows of the earlier stream stay
+ * in the tensor and are never read (a substitution reaches only rows committed since the reset), so after a reset the outputs are
+ * those of a new state, the tensor's ring slots need not be.
+ *   state: egr_trajectory_filter_state_slots(lag) x N x J doubles, laid out (slot, track), track = n * J + j; all zeros is the empty
+ *   stream; updated in place.  Slots: 0..10 the elimination's chain d1, d2, e1, f1, f2, y1[3], y2[3] after the last final row (t - 2);
+ *   11..15 frame t - 1 and 16..20 frame t: u, z[3], frames since the last observed one; 21 frames seen; 22 observed frames seen,
+ *   saturating at 2; 23 + 10 r .. 32 + 10 r the final row s with s mod lag = r: e, f, q[3], z[3], u, frames since the last observed
+ *   one.  Everything the arithmetic needs is there: a call can be captured into a graph once and replayed every frame.  Streams have
+ *   no length limit (slot 21 is exact up to 2^53 frames).
+ * One lane per track, fp64 on the fp32 operands, no atomics, a fixed order: a track's bits depend on its own operands only.
+ * EGR_EINVAL: N, C or J < 1, C > 4096, lag outside 0..64, N*C*J or N*J*slots >= 2^31, a penalty weight negative or not finite or both
+ * zero, gate negative or not finite, max_gap < 0. */
+int64_t egr_trajectory_filter_state_slots(int32_t lag); /* 23 + 10 lag; EGR_EINVAL for lag outside 0..64 */
+int egr_trajectory_filter_f32(const float* pose /* N x C x J x 3 */, const float* weight /* N x C x J, nullable */,
+                              const uint8_t* obs /* N x C x J, nullable */, const uint8_t* reset /* N, nullable */,
+                              double* state /* slots x N x J */, int32_t N, int32_t C, int32_t J, int32_t lag, float vel_weight,
+                              float accel_weight, float gate, int32_t max_gap, float* pose_out /* N x C x J x 3 */,
+                              uint8_t* valid /* N x C x J */, float* residual /* N x C x J */, float* weight_out /* N x C x J */,
+                              int64_t* frame /* N x C */, void* stream);
+/* The part no arrival has described yet: with T frames seen, rows 0..lag-1 are the frames T - lag .. T - 1 of x^(T-1), with the five
+ * outputs above; a row before the stream's start is zeros with frame -1.  The last row is the causal estimate of the present.  The
+ * state is read, not written.  lag == 0: no rows, nothing is launched. */
+int egr_trajectory_filter_tail_f32(const double* state /* slots x N x J */, int32_t N, int32_t J, int32_t lag, float vel_weight,
+                                   float accel_weight, int32_t max_gap, float* pose_out /* N x lag x J x 3 */,
+                                   uint8_t* valid /* N x lag x J */, float* residual /* N x lag x J */, float* weight_out /* N x lag x J */,
+                                   int64_t* frame /* N x lag */, void* stream);
+
 /* Rig self-calibration: the cameras' rotations refined from the decoded 2-D joints of a clip.  Over the pairs
  * (frame b, joint j), with the rays, weights and extrinsics of egr_triangulate_f32 (the same views used or excluded, w = conf),
  *   E(dR_0..dR_{V-1}) = sum_pairs min_p sum_v w_v |P(dR_v^T d_v) (R_v p + t_v)|^2 + prior_weight sum_v |dR_v - I|_F^2,  P(d) = I - d d^T,
